@@ -1,8 +1,15 @@
 """Benchmark of the north-star hot path: GP predict + acquisition (Sigma-UCB "HVI") + top-q.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what the headline figure needs and nothing else: set-up, W warm-up steps, K
+timed steps, the result line (`value`, `ms_per_step`, `selected`, the config).  --full adds, after
+the timed region, everything else described below: the fused kernel's own timing and `roofline`,
+`select_standalone`, `cpu_baseline` and the parity fields against it.  --dump-outputs DIR writes
+what the last timed step computed (DIR/<name>.npy, float64; DUMP_LIMIT_BYTES) so that two builds
+can be compared output for output: the inputs are seeded and identical from run to run.
 
 Workload (BASELINE.json configs[2], "C3"): 2-D / 2-objective toy_function
 (examples/benchmark_functions.py:33-50), N_train = 512, 1,048,576 candidates per GPU on the
@@ -18,9 +25,9 @@ fused predict/acquisition kernel writing mu, var and acq for every candidate, th
 merge) + the global top-q exchange + the indices on the host.  Inputs (X, y, K^-1) are
 resident in HBM before the timed region.
 
-Prints ONE JSON line (rank 0).  `roofline` is the fused kernel's matrix-core throughput over
-its HIP-event-timed launches: `achieved` counts the MFMA flops the kernel executes per candidate
-(the upper form q = 2 k.(U k) issues about half of SURVEY.md §8d's reference-formulation F), so
+Prints ONE JSON line (rank 0).  The --full fields: `roofline` is the fused kernel's matrix-core
+throughput over its HIP-event-timed launches: `achieved` counts the MFMA flops the kernel
+executes per candidate (the upper form q = 2 k.(U k) issues about half of SURVEY.md §8d's reference-formulation F), so
 `frac` <= 1 is a true fraction of the datasheet peak; the reference-formulation equivalent is
 reported separately as `ref_flop_equiv_tflops`.  `traffic` is the PMC-counted HBM bytes per
 launch and `traffic_ratio` its ratio to the algorithmic bytes.  `cpu_baseline` times the
@@ -207,6 +214,42 @@ def selection_check(sel_idx, cpu_acq, excluded, q):
         if not gap and abs(a[sel[t]] - top[t]) > 2 * tol[t]:
             return False
     return True
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000     # --dump-outputs: all files of one rank together
+
+
+def dump_sample_index(n_cand, values_per_cand, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the candidate columns written.  None = all of them (the arrays fit into
+    `limit` bytes as float64); else a fixed ascending sample of the candidate index, drawn with
+    `seed`, so large that values_per_cand float64 values per sampled candidate plus the sample's
+    own index array fit -- the same columns for every build and run.  64 KiB of the limit are
+    kept for the selection (at most BO_MAX_TOPQ = 48 points) and the .npy headers."""
+    limit -= 1 << 16
+    if 8 * values_per_cand * n_cand <= limit:
+        return None
+    k = limit // (8 * (values_per_cand + 1))
+    return np.sort(np.random.default_rng(seed).choice(n_cand, size=int(k), replace=False))
+
+
+def dump_outputs(path, out, sel, suffix=""):
+    """--dump-outputs: the arrays a caller of the timed step receives, as left by the last timed
+    step -- every per-candidate output (`out`: name -> device tensor [..., n_cand]) and the step's
+    returned selection -- as float64 .npy files (`sample_index.npy` when the candidates are
+    sampled; the selection indices are exact in float64).  All files of one call together stay
+    within DUMP_LIMIT_BYTES."""
+    os.makedirs(path, exist_ok=True)
+    n_cand = next(iter(out.values())).shape[-1]
+    idx = dump_sample_index(n_cand, sum(t.numel() // n_cand for t in out.values()))
+    save = lambda name, a: np.save(os.path.join(path, f"{name}{suffix}.npy"),  # noqa: E731
+                                   np.ascontiguousarray(a, dtype=np.float64))
+    if idx is not None:
+        save("sample_index", idx)
+    for name, t in out.items():
+        a = t.cpu().numpy()
+        save(name, a if idx is None else a[..., idx])
+    save("selected_values", sel[0])
+    save("selected_indices", sel[1])
 
 
 def cpu_baseline(x, y, pm, pv, ls, betas, kinv, points, label, q, max_cand=SIDE * SIDE, chunk=32768,
@@ -575,9 +618,17 @@ def main():
                          "through BayesianOptimization with the reference's timings)")
     ap.add_argument("--iteration", action="store_true",
                     help="time whole drop-in loop iterations (fit + kernels + acquisition + eval) at the config")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure and check what the headline figure does not "
+                         "need: the fused kernel's own timing (roofline), select_standalone, cpu_baseline "
+                         "and the parity fields against it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (every per-candidate output array and "
+                         "the selection) as DIR/<name>.npy in float64, at most 64 MB in all (a fixed "
+                         "seeded sample of the candidates above that)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline leg")
     ap.add_argument("--cpu-full", action="store_true",
-                    help="score the whole shard on the CPU for the parity fields even above 2^21 "
+                    help="--full: score the whole shard on the CPU for the parity fields even above 2^21 "
                          "candidates (C5: minutes of host time, outside the timed region)")
     ap.add_argument("--no-graph", action="store_true", help="launch the step's kernels directly "
                     "instead of replaying them as one HIP graph")
@@ -601,6 +652,9 @@ def main():
     if args.mode is None:
         args.mode = "fp32" if args.config == "C5" else "auto"
     cfg = CONFIGS.get(args.config)
+    if args.dump_outputs and (args.config == "C1" or args.iteration or args.fit or args.fit_demo):
+        raise SystemExit("--dump-outputs writes the predict + acquisition step's outputs "
+                         "(not --config C1, --iteration, --fit, --fit-demo)")
 
     import torch
     import torch.distributed as dist
@@ -806,15 +860,21 @@ def main():
     local_sel = rec.cpu()[q:].view(torch.int64).numpy() if use_dist else np.asarray(sel[1])
     local_sel = local_sel[local_sel >= 0]
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, sel, f"_rank{rank}" if world > 1 else "")
     import ctypes
     kms, nl = ctypes.c_double(), ctypes.c_int()
-    if graphed:
+    if graphed and args.full:
         # the fused kernel's launch duration: HIP events on its stream over as many direct calls
         lib.bo_profile_start(args.steps)
         for _ in range(args.steps):
             predict()
         torch.cuda.synchronize()
-    lib.bo_profile_stop(ctypes.byref(kms), ctypes.byref(nl))
+    # the kernel's own time: from the timed steps themselves when they were direct launches, from
+    # --full's extra direct calls when they were graph replays (a plain graphed run has none)
+    kernel_timed = args.full or not graphed
+    if kernel_timed:
+        lib.bo_profile_stop(ctypes.byref(kms), ctypes.byref(nl))
     t_step = dt / args.steps
     hv_front = None
     if args.acq == "hvi":
@@ -832,29 +892,10 @@ def main():
 
     if rank == 0:
         n, d = cfg["n_train"], cfg["dim"]
-        f = flops_per_candidate(n, n_obj, d)
-        fx = executed_mfma_flops_per_candidate(args.mode, n, n_obj)
-        executed = fx * per_rank / (k_ms * 1e-3) / 1e12
-        ref_equiv = f * per_rank / (k_ms * 1e-3) / 1e12
         metric = ("candidate-points/sec (GP predict + HVI) at N_train=512, N_cand=1M" if args.config == "C3"
                   else f"candidate-points/sec (GP predict + HVI), BASELINE config {args.config}")
         if args.acq == "hvi":
             metric += " [acquisition: exact hypervolume improvement, not the reference's sum of UCBs]"
-        peak = PEAK_F32_MATRIX_TFLOPS if args.mode == "fp32" else PEAK_F64_MATRIX_TFLOPS
-        # algorithmic HBM bytes per candidate: outputs written (+ explicit coordinates read)
-        n_out = sum(1 if k == "acq" else n_obj for k in outputs)
-        alg_bytes = (8 * n_out + (0 if cand[0] == "grid" else 8 * d)) * per_rank
-        # the PMC summary key: the config in its default precision, "-<mode>" otherwise
-        pmc_key = args.config if args.mode == ("fp32" if args.config == "C5" else "auto") \
-            else f"{args.config}-{args.mode}"
-        traffic, traffic_src = pmc_traffic(pmc_key) if args.acq == "sum_ucb" else \
-            (None, "not measured: the committed PMC passes run the sum-of-UCB step (this step writes "
-                   "the per-objective UCB the exact HVI reads)")
-        if world > 1 and traffic is not None:
-            # the committed PMC summaries are single-GPU runs over the whole candidate set: not
-            # this rank's per-launch traffic
-            traffic, traffic_src = None, (f"not measured per rank: {traffic_src} is a single-GPU "
-                                          f"summary of the whole candidate set")
         res = {
             "metric": metric,
             "value": total / t_step,
@@ -873,26 +914,47 @@ def main():
                        "n_cand_total": total, "n_objectives": n_obj, "dim": d, "topq": q,
                        "parallelism": f"candidate-shard x{world}", "step_launch": step_launch,
                        "candidate_offset": offset},
-            "roofline": {"bound": "mfma", "achieved": executed, "peak": peak, "unit": "TFLOP/s",
-                         "frac": executed / peak,
-                         "flops_basis": f"executed MFMA flops per candidate ({fx}; "
-                                        f"{'upper form' if args.mode != 'dense' else 'dense form'})",
-                         "traffic": traffic,
-                         "traffic_source": traffic_src or "no PMC summary of this libbo_amd.so build",
-                         "algorithmic_bytes": alg_bytes,
-                         "traffic_ratio": (traffic / alg_bytes) if traffic else None,
-                         "kernel": (f"cm32_predict_kernel<{2 if d <= 2 else 6}>" if args.mode == "fp32" else
-                                    f"cm_predict_kernel<{2 if d <= 2 else 6}, {'true' if cand[0] == 'grid' else 'false'}, "
-                                    f"{'true' if args.mode == 'auto' else 'false'}>"),
-                         "kernel_ms": k_ms,
-                         "formulation": ("upper: q = 2 k.(U k), U = triu((K^-1 + K^-T)/2), diag/2" if args.mode == "auto"
-                                         else "upper form in f32 (mu, q accumulated in f32, the rest f64)"
-                                         if args.mode == "fp32" else "dense: q = k^T (K^-1 k)"),
-                         "executed_mfma_flops_per_candidate": fx,
-                         "ref_flops_per_candidate": f,
-                         "ref_flop_equiv_tflops": ref_equiv},
             "selected": [int(i) for i in sel[1]],
         }
+        if kernel_timed:
+            # the fused kernel's own throughput and traffic (its event-timed launches)
+            f = flops_per_candidate(n, n_obj, d)
+            fx = executed_mfma_flops_per_candidate(args.mode, n, n_obj)
+            executed = fx * per_rank / (k_ms * 1e-3) / 1e12
+            ref_equiv = f * per_rank / (k_ms * 1e-3) / 1e12
+            peak = PEAK_F32_MATRIX_TFLOPS if args.mode == "fp32" else PEAK_F64_MATRIX_TFLOPS
+            # algorithmic HBM bytes per candidate: outputs written (+ explicit coordinates read)
+            n_out = sum(1 if k == "acq" else n_obj for k in outputs)
+            alg_bytes = (8 * n_out + (0 if cand[0] == "grid" else 8 * d)) * per_rank
+            # the PMC summary key: the config in its default precision, "-<mode>" otherwise
+            pmc_key = args.config if args.mode == ("fp32" if args.config == "C5" else "auto") \
+                else f"{args.config}-{args.mode}"
+            traffic, traffic_src = pmc_traffic(pmc_key) if args.acq == "sum_ucb" else \
+                (None, "not measured: the committed PMC passes run the sum-of-UCB step (this step writes "
+                       "the per-objective UCB the exact HVI reads)")
+            if world > 1 and traffic is not None:
+                # the committed PMC summaries are single-GPU runs over the whole candidate set: not
+                # this rank's per-launch traffic
+                traffic, traffic_src = None, (f"not measured per rank: {traffic_src} is a single-GPU "
+                                              f"summary of the whole candidate set")
+            res["roofline"] = {"bound": "mfma", "achieved": executed, "peak": peak, "unit": "TFLOP/s",
+                               "frac": executed / peak,
+                               "flops_basis": f"executed MFMA flops per candidate ({fx}; "
+                                              f"{'upper form' if args.mode != 'dense' else 'dense form'})",
+                               "traffic": traffic,
+                               "traffic_source": traffic_src or "no PMC summary of this libbo_amd.so build",
+                               "algorithmic_bytes": alg_bytes,
+                               "traffic_ratio": (traffic / alg_bytes) if traffic else None,
+                               "kernel": (f"cm32_predict_kernel<{2 if d <= 2 else 6}>" if args.mode == "fp32" else
+                                          f"cm_predict_kernel<{2 if d <= 2 else 6}, {'true' if cand[0] == 'grid' else 'false'}, "
+                                          f"{'true' if args.mode == 'auto' else 'false'}>"),
+                               "kernel_ms": k_ms,
+                               "formulation": ("upper: q = 2 k.(U k), U = triu((K^-1 + K^-T)/2), diag/2" if args.mode == "auto"
+                                               else "upper form in f32 (mu, q accumulated in f32, the rest f64)"
+                                               if args.mode == "fp32" else "dense: q = k^T (K^-1 k)"),
+                               "executed_mfma_flops_per_candidate": fx,
+                               "ref_flops_per_candidate": f,
+                               "ref_flop_equiv_tflops": ref_equiv}
         if args.acq == "hvi":
             torch.cuda.synchronize()
             hms = float(np.mean([a.elapsed_time(b) for a, b in hvi_ev[-args.steps:]]))
@@ -901,9 +963,9 @@ def main():
                                         "method": f"bo_box_volume_sum over this rank's share of the "
                                                   f"{n_boxes[0]} boxes + all_reduce(SUM) over {world} rank(s)"}
             # device time per call as select_standalone takes it: the step's masked call replayed
-            # as one HIP graph (no host launch gaps), after the timed region
+            # as one HIP graph (no host launch gaps), after the timed region (--full)
             hvi_graph_ms = None
-            if not args.hvi_unmasked:
+            if args.full and not args.hvi_unmasked:
                 boxes_g = torch.as_tensor(hypervolume_boxes(front_y, ref_pt), device=dev)
 
                 def hvi_call(strm):
@@ -944,10 +1006,10 @@ def main():
                                  "bytes_per_candidate": 8 * n_obj + 8,
                                  "achieved_GBps": hb / (hms * 1e-3) / 1e9,
                                  "hbm_frac": hb / (hms * 1e-3) / 1e9 / 8000.0}
-        if args.acq == "sum_ucb" and q <= 16:
+        if args.full and args.acq == "sum_ucb" and q <= 16:
             res["select_standalone"] = standalone_select(lib, bo, out["acq"], cands, offset, per_rank, xd,
                                                          q, dev, local_sel)
-        if world == 1 and not args.no_cpu_baseline and args.acq == "sum_ucb":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.acq == "sum_ucb":
             if cand[0] == "grid":
                 side = cand[2]
 

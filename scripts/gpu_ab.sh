@@ -5,6 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$R"
 mkdir -p gpurun_out
 LIBS=${LIBS:-$(ls bayesopt_smart_amd/libbo_amd*.so)}
+BENCH_ARGS="--full ${BENCH_ARGS}"   # the roofline fields read below
 : > gpurun_out/ab.jsonl
 for lib in $LIBS; do
   BO_AMD_LIB=$R/$lib timeout -k 10 300 python bench.py --no-cpu-baseline ${BENCH_ARGS} > gpurun_out/ab_one.json 2> gpurun_out/ab_err.log; rc=$?

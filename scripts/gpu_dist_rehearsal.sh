@@ -9,13 +9,13 @@ out=gpurun_out/dist/rehearsal.jsonl
 : > $out
 port=29511
 for c in ${CFGS:-C3 C4}; do
-  timeout -k 10 300 python bench.py --config $c --steps 3 --warmup 1 --no-cpu-baseline \
+  timeout -k 10 300 python bench.py --full --config $c --steps 3 --warmup 1 --no-cpu-baseline \
       > gpurun_out/dist/${c}_p1.log 2>&1 || { echo "fail $c p1"; tail -5 gpurun_out/dist/${c}_p1.log; exit 1; }
   grep '^{' gpurun_out/dist/${c}_p1.log | tail -1 >> $out
   for p in 2 4; do
     port=$((port + 1))
     BO_BENCH_BACKEND=gloo timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node $p \
-        --master-addr 127.0.0.1 --master-port $port bench.py --gpus $p --config $c --steps 3 --warmup 1 \
+        --master-addr 127.0.0.1 --master-port $port bench.py --full --gpus $p --config $c --steps 3 --warmup 1 \
         > gpurun_out/dist/${c}_p$p.log 2>&1 || { echo "fail $c p$p"; tail -5 gpurun_out/dist/${c}_p$p.log; exit 1; }
     grep '^{' gpurun_out/dist/${c}_p$p.log | tail -1 >> $out
   done

@@ -43,22 +43,22 @@ case $PHASE in
     step gpu_tests 1100 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -rf
     step smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
   bench)
-    step bench_c3_default 600 python bench.py
-    step bench_c2 300 python bench.py --config C2 --steps 20 --warmup 5
-    step bench_c4 400 python bench.py --config C4 --steps 5 --warmup 2
-    step bench_c5 400 python bench.py --config C5 --steps 3 --warmup 2 --no-cpu-baseline
-    step bench_c5f64 400 python bench.py --config C5 --mode auto --steps 3 --warmup 2 --no-cpu-baseline
-    step bench_c3_hvi 300 python bench.py --acq hvi --steps 5 --warmup 2 --no-cpu-baseline
+    step bench_c3_default 600 python bench.py --full
+    step bench_c2 300 python bench.py --full --config C2 --steps 20 --warmup 5
+    step bench_c4 400 python bench.py --full --config C4 --steps 5 --warmup 2
+    step bench_c5 400 python bench.py --full --config C5 --steps 3 --warmup 2 --no-cpu-baseline
+    step bench_c5f64 400 python bench.py --full --config C5 --mode auto --steps 3 --warmup 2 --no-cpu-baseline
+    step bench_c3_hvi 300 python bench.py --full --acq hvi --steps 5 --warmup 2 --no-cpu-baseline
     step bench_c1 300 python bench.py --config C1 ;;
   pmc1)
-    pmc c3 $B --steps 1 --warmup 1 --no-cpu-baseline
-    pmc c2 $B --config C2 --steps 1 --warmup 1 --no-cpu-baseline
-    pmc c4 $B --config C4 --steps 1 --warmup 1 --no-cpu-baseline
-    stats c3 $B --steps 10 --warmup 3 --no-cpu-baseline
-    stats c2 $B --config C2 --steps 20 --warmup 5 --no-cpu-baseline ;;
+    pmc c3 $B --full --steps 1 --warmup 1 --no-cpu-baseline
+    pmc c2 $B --full --config C2 --steps 1 --warmup 1 --no-cpu-baseline
+    pmc c4 $B --full --config C4 --steps 1 --warmup 1 --no-cpu-baseline
+    stats c3 $B --full --steps 10 --warmup 3 --no-cpu-baseline
+    stats c2 $B --full --config C2 --steps 20 --warmup 5 --no-cpu-baseline ;;
   pmc2)
-    pmc c5 $B --config C5 --steps 1 --warmup 1 --no-cpu-baseline
-    pmc c5f64 $B --config C5 --mode auto --steps 1 --warmup 1 --no-cpu-baseline ;;
+    pmc c5 $B --full --config C5 --steps 1 --warmup 1 --no-cpu-baseline
+    pmc c5f64 $B --full --config C5 --mode auto --steps 1 --warmup 1 --no-cpu-baseline ;;
   iter)
     step fit_c3 300 python bench.py --fit --config C3
     step fit_c4 300 python bench.py --fit --config C4
@@ -69,9 +69,9 @@ case $PHASE in
     stats fit $B --fit --config C3 ;;
   c5cpu)      # C5 (fp32, the config's stated precision) with cpu_baseline and the whole set scored on
               # the host cores for selection_matches_cpu (--cpu-full: 4,194,304 candidates at N = 2048)
-    step bench_c5_cpufull 1100 python -u bench.py --config C5 --steps 3 --warmup 2 --cpu-full ;;
+    step bench_c5_cpufull 1100 python -u bench.py --full --config C5 --steps 3 --warmup 2 --cpu-full ;;
   c5cpu64)
-    step bench_c5f64_cpufull 1100 python -u bench.py --config C5 --mode auto --steps 3 --warmup 2 --cpu-full ;;
+    step bench_c5f64_cpufull 1100 python -u bench.py --full --config C5 --mode auto --steps 3 --warmup 2 --cpu-full ;;
   dist)       # bench.py's multi-rank step rehearsed on one device (gloo, P = 1, 2, 4), C2 C3 C4 C5
     CFGS="C2 C3 C4 C5" step dist_rehearsal 1100 bash scripts/gpu_dist_rehearsal.sh
     cp gpurun_out/dist/rehearsal.jsonl "$OUT/dist_rehearsal.jsonl" ;;

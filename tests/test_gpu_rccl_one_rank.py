@@ -41,7 +41,7 @@ def _json_line(out):
 
 
 def test_bench_step_over_rccl_one_rank():
-    args = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    args = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     got = _json_line(_run(args, True))
     ref = _json_line(_run(args, False))
     assert got["collectives"]["backend"] == "nccl" and got["collectives"]["world_size"] == 1, got.get("collectives")
