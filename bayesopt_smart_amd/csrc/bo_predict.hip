@@ -343,6 +343,9 @@ struct PrepArgs {
   int* sep_flag;                         // NULL: no separable grid check
   long long sep_lo;
   int sep_S;
+  int* conv_flag;                        // NULL: no grid-convolution check (bo_gridconv.hip)
+  long long conv_lo[2];
+  int conv_ext[2];
   double* excl;
   const double* excl_in;
   int n_excl;
@@ -360,7 +363,7 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
   int b = blockIdx.x;
   if (b == 0) {
     if (!p.rows) return;
-    int sep_bad = 0;
+    int sep_bad = 0, conv_bad = 0;
     for (int f = tid; f < p.n_pad; f += 256) {
       for (int k = 0; k < p.DIM; ++k) {
         const bool real = f < p.n && k < p.dim;
@@ -373,9 +376,20 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
         const bool ok = v == __builtin_rint(v) && v >= (double)p.sep_lo && v <= (double)(p.sep_lo + p.sep_S - 1);
         sep_bad |= !ok;
       }
+      // grid-convolution precondition: the training point is a point of the 2-D grid
+      if (f < p.n && p.conv_flag) {
+        for (int k = 0; k < 2; ++k) {
+          const double v = p.x[(long long)f * p.dim + k];
+          const bool ok = v == __builtin_rint(v) && v >= (double)p.conv_lo[k] &&
+                          v <= (double)(p.conv_lo[k] + p.conv_ext[k] - 1);
+          conv_bad |= !ok;
+        }
+      }
     }
     const int any_bad = __syncthreads_or(sep_bad);
     if (tid == 0 && p.sep_flag) *p.sep_flag = any_bad ? 1 : 0;
+    const int any_conv_bad = __syncthreads_or(conv_bad);
+    if (tid == 0 && p.conv_flag) *p.conv_flag = any_conv_bad ? 1 : 0;
     for (int t = tid; t < p.n_excl * p.DIM; t += 256) {
       const int r = t / p.DIM, k = t - r * p.DIM;
       p.excl[t] = k < p.dim ? p.excl_in[(long long)r * p.dim + k] : 0.0;
@@ -476,6 +490,69 @@ int num_cus() {
   return cus;
 }
 
+// The grid-convolution path (bo_gridconv.hip): planned for a 2-D integer grid in the
+// default (upper, separable, f64) mode when its kernels' tables fit the LDS and the cost gate
+// passes; whether the training points are grid points is known only on the device (conv flag).
+//   gate: margin x (modelled time of the new sequence) < modelled time of the chunk-major kernel.
+//   A ratio of matrix-core flops does not predict the crossover (measured, DESIGN.md §9: at a
+//   64 x 64 grid the flop ratio is 5-8 and the new path 3-14x SLOWER): the new path has fixed
+//   launches, its pair stage is one serial wave per tau, and small grids leave most SIMDs idle in
+//   both paths.  The model, in microseconds on MI355X (256 CUs), constants fitted to that table:
+//     new  = 60 + 2.2 x (pairs per tau) x (1024-row blocks) x (rounds of 4096 tau-waves)
+//               + (rounds of 1024 wave tiles) x 2 x 16 x 64 x (LT + NP) x n_obj / 48.8e3
+//            (the contraction at its measured 50 TF: 48.8e3 flops per us and wave slot)
+//     old  = 25 + (rounds of 256 tiles of 64 candidates) x 64 x (F / 273e3 + 0.038),
+//            F = n_obj 1024 nch (nch + 1) MFMA flops per candidate at the measured 70 TF.
+//   Both sides reproduce the 15 measured points within 20 %; the margin covers that.
+//   BO_PREDICT_GRID_CONV skips the gate, BO_PREDICT_NO_GRID_CONV and BO_GRID_CONV=0 (environment,
+//   read here: fixed when a graph is captured) never plan it.
+constexpr double kConvMargin = 1.15;
+constexpr int kConvMaxN = 4096;          // conv_setup_kernel ranks a point against all earlier ones
+
+void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
+  if (kmem || !pl->cm || d->cand_kind != BO_CAND_GRID || d->dim != 2 || d->n_cand <= 0) return;
+  if (d->mode & (BO_PREDICT_DENSE | BO_PREDICT_NO_SEPARABLE | BO_PREDICT_FP32 | BO_PREDICT_NO_GRID_CONV)) return;
+  const char* env = getenv("BO_GRID_CONV");
+  if (env && env[0] == '0' && env[1] == 0) return;
+  const long long R = d->grid_shape[0], C = d->grid_shape[1], n = d->n_train;
+  if (R < 1 || C < 1 || R > (1 << 15) || C > (1 << 15) || n > kConvMaxN) return;
+  if (d->cand_offset < 0 || d->cand_offset + d->n_cand > R * C) return;
+  if (bo::conv_lds_setup((int)n, (int)C) > kLdsBytes || bo::conv_lds_pair((int)n, (int)R, (int)C) > kLdsBytes ||
+      bo::conv_lds_contract((int)n, (int)C) > kLdsBytes)
+    return;
+  const long long row_lo = d->cand_offset / C, row_hi = (d->cand_offset + d->n_cand - 1) / C;
+  const long long nrows = row_hi - row_lo + 1;
+  if (!(d->mode & BO_PREDICT_GRID_CONV)) {
+    const double nch = pl->n_pad / 32;
+    const double F = (double)d->n_obj * 1024.0 * nch * (nch + 1);
+    const double old_rounds = (double)(((d->n_cand + 63) / 64 + 255) / 256);
+    const double old_us = 25.0 + old_rounds * 64.0 * (F / 273.0e3 + 0.038);
+    const long long ldr = (nrows + 15) / 16 * 16, Cpad = (C + 63) / 64 * 64;
+    const long long LT = (2 * C - 1 + 15) / 16 * 16, NP = (n + 15) / 16 * 16;
+    const double pairs_per_tau = 0.5 * (double)n * (double)(n + 1) / (double)(2 * C - 1);
+    const double pair_us = 2.2 * pairs_per_tau * (double)((ldr + 1023) / 1024) *
+                           (double)((d->n_obj * (2 * C - 1) + 4095) / 4096);
+    const double tile_rounds = (double)(((ldr / 16) * (Cpad / 64) + 1023) / 1024);
+    const double contract_us = tile_rounds * 2048.0 * (double)(LT + NP) * (double)d->n_obj / 48.8e3;
+    const double conv_us = 60.0 + pair_us + contract_us;
+    if (!(kConvMargin * conv_us < old_us)) return;
+  }
+  pl->conv = true;
+  pl->conv_row_lo = (int)row_lo;
+  pl->conv_nrows = (int)nrows;
+  pl->conv_ldr = (int)((nrows + 15) / 16 * 16);
+  pl->conv_LT = (int)((2 * C - 1 + 15) / 16 * 16);
+  pl->conv_NP = (int)((n + 15) / 16 * 16);
+  pl->conv_Cpad = (int)((C + 63) / 64 * 64);
+  const long long n_wt = (long long)(pl->conv_ldr / 16) * (pl->conv_Cpad / 64);
+  const long long wgs = (n_wt + 3) / 4;
+  pl->conv_grid = (int)(wgs < pl->grid ? wgs : pl->grid);
+  pl->off_conv_ints = align256(pl->total);
+  pl->off_conv_Tm = pl->off_conv_ints + align256((size_t)(C + 1 + 3 * n) * sizeof(int));
+  pl->off_conv_T = pl->off_conv_Tm + align256((size_t)d->n_obj * pl->conv_NP * pl->conv_ldr * sizeof(double));
+  pl->total = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
+}
+
 // Kernel choice and workspace layout of one call.
 //   fp32: cm32_predict_kernel (rows + alpha in LDS as f32; falls back to the f64 kernel when
 //         they do not fit);
@@ -489,7 +566,9 @@ int make_plan(const bo_predict_desc* d, Plan* pl, bool query_device, bool kmem =
     return BO_ERR_ARG;
   if (d->n_train < 1 || d->n_cand < 0 || d->topq < 0 || d->topq > BO_MAX_TOPQ) return BO_ERR_ARG;
   if (d->cand_kind < 0 || d->cand_kind > BO_CAND_SOBOL) return BO_ERR_ARG;
-  if (d->mode & ~(BO_PREDICT_DENSE | BO_PREDICT_NO_SEPARABLE | BO_PREDICT_FP32 | BO_PREDICT_F32_FLOOR)) return BO_ERR_ARG;
+  if (d->mode & ~(BO_PREDICT_DENSE | BO_PREDICT_NO_SEPARABLE | BO_PREDICT_FP32 | BO_PREDICT_F32_FLOOR |
+                  BO_PREDICT_NO_GRID_CONV | BO_PREDICT_GRID_CONV))
+    return BO_ERR_ARG;
   if (d->excl_points && d->n_excl < 0) return BO_ERR_ARG;
   const long long n = d->n_train;
   if (n > (1 << 14)) return BO_ERR_UNSUPPORTED;
@@ -590,7 +669,8 @@ int make_plan(const bo_predict_desc* d, Plan* pl, bool query_device, bool kmem =
   // partial lists sized for the largest persistent grid any device could use
   pl->off_status = pl->off_partial +
                    align256((size_t)1024 * kWaves * (d->topq > 0 ? d->topq : 1) * sizeof(TopEntry));
-  pl->total = pl->off_status + 256 + 256;   // +16: separable-K* flag
+  pl->total = pl->off_status + 256 + 256;   // +16: separable-K* flag, +32: grid-convolution flag
+  plan_gridconv(d, pl, kmem);
   return BO_OK;
 }
 
@@ -661,6 +741,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   double* excl = (double*)(ws + pl.off_excl);
   TopEntry* partial = (TopEntry*)(ws + pl.off_partial);
   int* sep_flag = (int*)(ws + pl.off_status + 16);
+  int* conv_flag = (int*)(ws + pl.off_status + 32);
 
   FusedArgs fa;
   memset(&fa, 0, sizeof(fa));
@@ -741,6 +822,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   fa.rw_cache = pl.rw_cache ? 1 : 0;
   fa.rw_stride = pl.rw_stride;
   fa.off_exp = pl.off_exp;
+  fa.conv_flag = pl.conv ? conv_flag : nullptr;
   {
     PrepArgs pa;
     memset(&pa, 0, sizeof(pa));
@@ -771,6 +853,11 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     pa.sep_flag = pl.sep ? sep_flag : nullptr;
     pa.sep_lo = fa.sep_lo;
     pa.sep_S = fa.sep_S;
+    pa.conv_flag = pl.conv ? conv_flag : nullptr;
+    for (int k = 0; k < 2; ++k) {
+      pa.conv_lo[k] = d->grid_lo[k];
+      pa.conv_ext[k] = (int)d->grid_shape[k];
+    }
     pa.excl = excl;
     pa.excl_in = d->excl_points;
     pa.n_excl = (kmem || !d->excl_points) ? 0 : pl.n_excl;
@@ -793,6 +880,61 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   hipError_t e;
   const bool timed = g_timer.on && g_timer.used + 2 <= (int)g_timer.ev.size();
   if (timed) timer_mark(s);
+  if (pl.conv) {
+    // the grid-convolution kernels and the chunk-major kernel are both enqueued; the device flag
+    // lets one of them run (no host synchronisation: the call stays capturable)
+    bo::ConvArgs ca;
+    memset(&ca, 0, sizeof(ca));
+    ca.n_obj = d->n_obj;
+    ca.n = (int)d->n_train;
+    ca.n_pad = pl.n_pad;
+    ca.R = (int)d->grid_shape[0];
+    ca.C = (int)d->grid_shape[1];
+    ca.lo0 = d->grid_lo[0];
+    ca.lo1 = d->grid_lo[1];
+    ca.cand_offset = d->cand_offset;
+    ca.n_cand = d->n_cand;
+    ca.ld_out = fa.ld_out;
+    ca.row_lo = pl.conv_row_lo;
+    ca.nrows = pl.conv_nrows;
+    ca.ldr = pl.conv_ldr;
+    ca.LT = pl.conv_LT;
+    ca.NP = pl.conv_NP;
+    ca.Cpad = pl.conv_Cpad;
+    ca.flag = conv_flag;
+    ca.x = d->x_train;
+    ca.kinv = d->kinv;
+    ca.ld_k = d->ld_k;
+    ca.alpha = alpha;
+    for (int o = 0; o < d->n_obj; ++o) {
+      ca.pm[o] = fa.pm[o];
+      ca.pv[o] = fa.pv[o];
+      ca.nhl[o] = fa.nhl[o];
+      ca.beta[o] = fa.beta[o];
+      ca.inv_rsq_pv[o] = fa.inv_rsq_pv[o];
+      ca.inv_pv[o] = fa.inv_pv[o];
+    }
+    ca.min_var = fa.min_var;
+    ca.cstart = (int*)(ws + pl.off_conv_ints);
+    ca.order = ca.cstart + (ca.C + 1);
+    ca.rc = ca.order + ca.n;
+    ca.Tm = (double*)(ws + pl.off_conv_Tm);
+    ca.T = (double*)(ws + pl.off_conv_T);
+    ca.mu = d->mu;
+    ca.var = d->var;
+    ca.std_mu = d->std_mu;
+    ca.std_var = d->std_var;
+    ca.ucb = d->ucb;
+    ca.acq = d->acq;
+    ca.topq = d->topq;
+    ca.partial = partial;
+    ca.n_lists = pl.grid * pl.waves;
+    ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
+    ca.hkeys = fa.hkeys;
+    ca.hidx = fa.hidx;
+    ca.hmask = fa.hmask;
+    if (bo::launch_gridconv(ca, pl.conv_grid, s) != hipSuccess) return BO_ERR_HIP;
+  }
   if (kmem) e = launch_kmem(pl, fa, s);
   else if (pl.fp32) switch (pl.dim_pad) {
     case 2: e = bo::launch_c32_d2(pl, fa, s); break;

@@ -66,7 +66,50 @@ struct FusedArgs {
   const unsigned long long* hkeys;       // hash set of the exclusion rows (excl or xpad), built
   const int* hidx;                       // by the prep launch (bo_point_key over DIM coordinates)
   unsigned int hmask;
+  // grid-convolution path (bo_gridconv.hip) planned for this call: device flag, 0 => that path
+  // runs and cm_predict_kernel returns at once; NULL => not planned
+  const int* conv_flag;
 };
+
+// Arguments of the grid-convolution path (bo_gridconv.hip): 2-D integer grid
+// [R][C], every training point a grid point.  Coordinates are integers relative to grid_lo.
+struct ConvArgs {
+  int n_obj, n, n_pad;                   // n_pad: row stride of alpha
+  int R, C;                              // grid extents (axis 0, axis 1)
+  long long lo0, lo1;
+  long long cand_offset, n_cand, ld_out;
+  int row_lo, nrows, ldr;                // grid rows touched by the shard; ldr = nrows padded to 16
+  int LT;                                // tau extent 2C - 1 padded to 16 (rows of T)
+  int NP;                                // n padded to 16 (rows of Tm)
+  int Cpad;                              // C padded to the wave tile's 64 columns
+  const int* flag;                       // 0 => every training point is a grid point
+  const double* x;                       // [n][2] training points
+  const double* kinv;                    // [n_obj][ld_k][ld_k]
+  long long ld_k;
+  const double* alpha;                   // [n_obj][n_pad]
+  double pm[BO_MAX_OBJ], pv[BO_MAX_OBJ], nhl[BO_MAX_OBJ], beta[BO_MAX_OBJ];
+  double inv_rsq_pv[BO_MAX_OBJ], inv_pv[BO_MAX_OBJ];
+  double min_var;
+  int* cstart;                           // [C + 1] first slot of each column's bucket
+  int* order;                            // [n] training points sorted by column (stable)
+  int* rc;                               // [n][2] integer coordinates (row, column)
+  double* T;                             // [n_obj][LT][ldr]
+  double* Tm;                            // [n_obj][NP][ldr]  pv alpha_n H(i - r_n)
+  double *mu, *var, *std_mu, *std_var, *ucb, *acq;
+  int topq;
+  TopEntry* partial;                     // [n_lists][topq]
+  int n_lists;                           // lists the merge reads (those past the grid's are emptied)
+  const double* excl_pts;                // rows the hash set indexes ([*][2])
+  const unsigned long long* hkeys;
+  const int* hidx;
+  unsigned int hmask;
+};
+
+// LDS bytes of the three kernels; launch of the whole sequence (setup, pair stage, contraction)
+size_t conv_lds_setup(int n, int C);
+size_t conv_lds_pair(int n, int R, int C);
+size_t conv_lds_contract(int n, int C);
+hipError_t launch_gridconv(const ConvArgs& ca, int grid, hipStream_t st);
 
 // Host-side plan of one bo_predict_acquire call (bo_predict.hip: make_plan).
 struct Plan {
@@ -86,6 +129,10 @@ struct Plan {
   int grid, waves;       // persistent grid, waves per workgroup
   long long n_tiles;
   size_t lds;
+  bool conv;             // grid-convolution path planned (taken when the device flag allows)
+  int conv_grid;         // its contraction kernel's workgroups (<= grid: it fills the same lists)
+  int conv_row_lo, conv_nrows, conv_ldr, conv_LT, conv_NP, conv_Cpad;
+  size_t off_conv_T, off_conv_Tm, off_conv_ints;
 };
 
 // launch wrappers (one translation unit per padded dimension)
@@ -931,6 +978,8 @@ template <int DIM, bool GRID, bool UPPER, bool GROWS, int MAXEP, bool PART = fal
 __global__ __launch_bounds__(256, MAXEP <= 4 ? 2 : 1) void cm_predict_kernel(const FusedArgs a) {
   extern __shared__ __attribute__((aligned(16))) double smem[];
   const int tid = threadIdx.x;
+  // the grid-convolution kernels score this call (bo_gridconv.hip)
+  if (a.conv_flag && __builtin_amdgcn_readfirstlane(*a.conv_flag) == 0) return;
   const bool sep = !GROWS && GRID && __builtin_amdgcn_readfirstlane(*a.sep_flag) == 0;
   if (!GROWS) {
     // rows: original grid coordinates for the row pass (SEP), centred otherwise

@@ -102,12 +102,20 @@ int bo_device_count(void);
  * exp (no grid table); DENSE / NO_SEPARABLE are ignored with it. */
 /* BO_PREDICT_F32_FLOOR: the posterior variance floor of the reference's float32 branch,
  * MIN_VARIANCE = 1e-6 (config.py:57-61), instead of the fp64 branch's 1e-10 (:63-66). */
+/* Grid convolution (2-D integer grid whose training points are all grid points, checked on the
+ * device; AUTO form only): the quadratic form regrouped over the midpoints of the training
+ * pairs, q(i, j) = sum_tau T(i, tau) E(2j - tau), 2 (2C - 1) + 2N matrix-core flops per candidate
+ * and objective instead of N^2.  Planned when a cost gate passes; BO_PREDICT_GRID_CONV plans it
+ * whenever the shape allows, BO_PREDICT_NO_GRID_CONV (or BO_GRID_CONV=0 in the environment)
+ * never.  When the device check fails the call runs the chunk-major kernel as before. */
 typedef enum bo_predict_mode {
   BO_PREDICT_AUTO = 0,
   BO_PREDICT_DENSE = 1,
   BO_PREDICT_NO_SEPARABLE = 2,
   BO_PREDICT_FP32 = 4,
-  BO_PREDICT_F32_FLOOR = 8
+  BO_PREDICT_F32_FLOOR = 8,
+  BO_PREDICT_NO_GRID_CONV = 16,
+  BO_PREDICT_GRID_CONV = 32
 } bo_predict_mode;
 
 typedef struct bo_predict_desc {
