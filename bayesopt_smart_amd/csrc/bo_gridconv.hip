@@ -15,15 +15,19 @@
 // the same N^2 products as k' K^-1 k (update_variance, numba_kernels.py:491-535), grouped so that
 // a candidate costs 2 (2C - 1) + 2 N matrix-core flops per objective instead of N^2.
 //
-// Three launches, each returning at once unless the device flag (predict_prep_kernel) says that
+// Four launches, each returning at once unless the device flag (predict_prep_kernel) says that
 // every training point is a grid point:
 //   conv_setup_kernel     integer coordinates; training points bucketed by column (stable
-//                         counting sort);
-//   conv_pair_kernel      T (one wave per tau) and Tm[n][i] = pv alpha_n H(i - r_n);
+//                         counting sort); the pair stage's schedule: pairs per tau, their offsets
+//                         in the pair list, the tau by descending pair count, the tickets;
+//   conv_list_kernel      the pair list (one wave per tau): table base once, w_nm per objective;
+//                         and Tm[n][i] = pv alpha_n H(i - r_n);
+//   conv_acc_kernel       T: persistent waves take (tau, row block) items, longest lists first;
 //   conv_contract_kernel  the two GEMMs on v_mfma_f64_16x16x4_f64, the epilogue of
 //                         cm_predict_kernel, per-wave top-q lists in the TopEntry partial layout.
-// No floating-point atomics; every sum runs in an order fixed by the inputs alone, and the K
-// order of an output element does not depend on its tile, so shards reproduce the single call.
+// No floating-point atomics (the tickets are integers and order work, not sums); every sum runs
+// in an order fixed by the inputs alone, and the K order of an output element does not depend on
+// its tile, so shards reproduce the single call.
 
 #include "bo_predict_impl.h"
 
@@ -31,27 +35,94 @@ namespace {
 
 using bo::ConvArgs;
 
-constexpr int kPairChunk = 256;          // pairs of one tau held in LDS at a time (per wave)
-constexpr int kTauPerWg = 8;             // waves per workgroup of the pair stage, one tau each
-constexpr int kPairThreads = 64 * kTauPerWg;
-constexpr int kRowBlock = 16;            // rows per lane and pass of the pair stage
+// the LDS layout of the removed one-kernel pair stage, kept for conv_lds_pair alone (the plan's gate)
+constexpr int kPairChunk = 256;
+constexpr int kTauPerWg = 8;
+constexpr int kSetupThreads = 1024;
+constexpr int kSetupWaves = kSetupThreads / 64;
+constexpr int kListWaves = 4;            // waves per workgroup of the list kernel, one tau each
+constexpr int kListChunk = 512;          // pairs of one tau staged in LDS at a time (per wave)
+constexpr int kAccWaves = 4;             // waves per workgroup of the accumulate kernel
+// rows per lane of a work item.  BO_BUILD_VARIANT=DEF_ACC_RB=16 builds the other candidate (A/B in
+// DESIGN.md §9)
+#ifndef BO_ACC_RB
+#define BO_ACC_RB 8
+#endif
+constexpr int kAccRB = BO_ACC_RB;
+constexpr int kAccRows = 64 * kAccRB;    // rows of a work item (tau, row block)
+constexpr int kAccUnroll = 4;            // list entries loaded ahead of their terms
+// tickets per objective, each on a cache line of its own.  One ticket per objective made the kernel
+// as long as its atomics: ~25 ns each on one address from 8 XCDs, 6,000 of them at C3 (160 us)
+constexpr int kAccGroups = bo::kConvTicketGroups;
+constexpr int kTicketStride = bo::kConvTicketStride;
 constexpr int kConvPF = 3;               // A-operand prefetch depth of the contraction (k-blocks)
+constexpr size_t kConvLdsBytes = 160 * 1024;
+
+// exclusive scan of v[0 .. len) in place over the workgroup, also written to out (if given);
+// part[kSetupWaves].  Contiguous segments per thread, a wave scan of their sums, the waves' totals.
+__device__ __forceinline__ void setup_scan(int* v, int len, int* part, int* out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int seg = (len + kSetupThreads - 1) / kSetupThreads;
+  const int c_lo = tid * seg < len ? tid * seg : len, c_hi = c_lo + seg < len ? c_lo + seg : len;
+  int sum = 0;
+  for (int c = c_lo; c < c_hi; ++c) sum += v[c];
+  int incl = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) part[wave] = incl;
+  __syncthreads();
+  int run = incl - sum;
+  for (int w = 0; w < wave; ++w) run += part[w];
+  for (int c = c_lo; c < c_hi; ++c) {
+    const int t = v[c];
+    v[c] = run;
+    if (out) out[c] = run;
+    run += t;
+  }
+  __syncthreads();
+}
 
 // ---------------------------------------------------------------------------------------
 // Setup: rc[n] = integer (row, column) of training point n; cstart / order = the points bucketed
-// by column, ascending n inside a bucket.  One workgroup.
-// LDS: cnt[C + 1] | col[n] | part[256]
+// by column, ascending n inside a bucket; and the schedule of the pair stage: pstart[tau] = first
+// slot of tau's pairs in the pair list (tau's count = pstart[tau + 1] - pstart[tau]), torder = the
+// tau by descending pair count (ties by ascending tau), the accumulate kernel's tickets.
+// One workgroup.
+//   pairs per tau: every pair of non-empty columns c <= c' adds h[c] h[c'] (c < c') or
+//   h[c] (h[c] + 1) / 2 (c = c') to tau = c + c' (integer atomics in LDS);
+//   work order: a stable radix sort of the tau (ascending at the start) by 255 - digit, 8 bits a
+//   pass, as many passes as the largest count has digits (one at C3).  A wave owns a contiguous
+//   chunk of the sequence: per-(digit, wave) counts, one scan in (digit, wave) order, then the
+//   wave places its chunk 64 entries at a time (the lanes of equal digit found by 8 ballots keep
+//   their order).
+// LDS: cnt[C + 1] | col[n] | part[waves] | tcnt[LT + 1] | clist[min(n, C)] | nnz, max |
+//      wcnt[256][waves] | perm[2][LT] (16 bits each)
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void conv_setup_kernel(const ConvArgs a) {
+__global__ __launch_bounds__(kSetupThreads) void conv_setup_kernel(const ConvArgs a, int acc_wgs, int ngrp, int dyn) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   extern __shared__ __attribute__((aligned(16))) int si[];
   int* cnt = si;
   int* col = cnt + (a.C + 1);
   int* part = col + a.n;
-  const int tid = threadIdx.x;
-  for (int c = tid; c <= a.C; c += 256) cnt[c] = 0;
+  int* tcnt = part + kSetupWaves;
+  int* clist = tcnt + (a.LT + 1);
+  int* misc = clist + (a.n < a.C ? a.n : a.C);
+  int* wcnt = misc + 2;
+  unsigned short* perm = (unsigned short*)(wcnt + 256 * kSetupWaves);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  for (int c = tid; c <= a.C; c += kSetupThreads) cnt[c] = 0;
+  for (int t = tid; t <= a.LT; t += kSetupThreads) tcnt[t] = 0;
+  if (tid < 2) misc[tid] = 0;
+  // the first items of the accumulate kernel's waves are their own indices in their group
+  if (tid < a.n_obj * ngrp) {
+    const int g = tid % ngrp;
+    a.ticket[(tid / ngrp * kAccGroups + g) * kTicketStride] = (acc_wgs - g + ngrp - 1) / ngrp * kAccWaves;
+  }
   __syncthreads();
-  for (int n = tid; n < a.n; n += 256) {
+  for (int n = tid; n < a.n; n += kSetupThreads) {
     const int r = (int)(a.x[2 * (long long)n] - (double)a.lo0);
     const int c = (int)(a.x[2 * (long long)n + 1] - (double)a.lo1);
     a.rc[2 * n] = r;
@@ -60,101 +131,153 @@ __global__ __launch_bounds__(256) void conv_setup_kernel(const ConvArgs a) {
     atomicAdd(cnt + c, 1);
   }
   __syncthreads();
-  // exclusive scan of cnt[0 .. C]: contiguous segments per thread, then the 256 partial sums
-  const int seg = (a.C + 1 + 255) / 256;
-  const int c_lo = tid * seg, c_hi = c_lo + seg < a.C + 1 ? c_lo + seg : a.C + 1;
-  int sum = 0;
-  for (int c = c_lo; c < c_hi; ++c) sum += cnt[c];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {
-    const int v = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += v;
-    __syncthreads();
-  }
-  int run = part[tid] - sum;
-  for (int c = c_lo; c < c_hi; ++c) {
-    const int v = cnt[c];
-    cnt[c] = run;
-    a.cstart[c] = run;
-    run += v;
+  // the non-empty columns as (column, count) in 15 + 13 bits (C <= 2^15, n <= 4096); any order
+  for (int c = tid; c < a.C; c += kSetupThreads) {
+    const int h = cnt[c];
+    if (h > 0) clist[atomicAdd(misc, 1)] = c | (h << 15);
   }
   __syncthreads();
+  setup_scan(cnt, a.C + 1, part, a.cstart);
   // stable placement: the rank of n among the earlier points of its column
-  for (int n = tid; n < a.n; n += 256) {
+  for (int n = tid; n < a.n; n += kSetupThreads) {
     const int c = col[n];
     int rank = 0;
     for (int m = 0; m < n; ++m) rank += col[m] == c ? 1 : 0;
     a.order[cnt[c] + rank] = n;
   }
+  // pairs per tau (the K padding of the contraction and the scan's last entry stay 0): a wave per
+  // column c, the lanes over c' >= c, 8 reads in flight ahead of their atomics.  (Measured at C3,
+  // ~400 non-empty columns: 25 us, the longest part of this kernel; a gather form without atomics
+  // -- a thread per tau over the sorted non-empty columns -- took 32 us unrolled by 8, 48 us plain)
+  const int ncol = misc[0];
+  for (int i = wave; i < ncol; i += kSetupWaves) {
+    const int ei = clist[i], ci = ei & 32767, hi = ei >> 15;
+    for (int j0 = i + lane; j0 < ncol; j0 += 64 * 8) {
+      int ej[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) ej[u] = j0 + 64 * u < ncol ? clist[j0 + 64 * u] : -1;
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (ej[u] >= 0)
+          atomicAdd(tcnt + ci + (ej[u] & 32767), j0 + 64 * u == i ? hi * (hi + 1) / 2 : hi * (ej[u] >> 15));
+    }
+  }
+  __syncthreads();
+  {
+    int mx = 0;
+    for (int t = tid; t < a.LT; t += kSetupThreads) mx = tcnt[t] > mx ? tcnt[t] : mx;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      const int o = __shfl_xor(mx, d, 64);
+      mx = o > mx ? o : mx;
+    }
+    if (lane == 0) atomicMax(misc + 1, mx);
+  }
+  __syncthreads();
+  // (no more items than waves: every wave takes the one item of its index, and their order is moot)
+  const int npass = !dyn ? 0 : misc[1] < 256 ? 1 : misc[1] < 65536 ? 2 : 3;
+  const int chunk = ((a.LT + kSetupWaves - 1) / kSetupWaves + 63) / 64 * 64;
+  const int e_lo = wave * chunk, e_hi = e_lo + chunk < a.LT ? e_lo + chunk : a.LT;
+  unsigned short *pa = perm, *pb = perm + a.LT;
+  for (int pass = 0; pass < npass; ++pass) {
+    for (int t = tid; t < 256 * kSetupWaves; t += kSetupThreads) wcnt[t] = 0;
+    __syncthreads();
+    for (int e = e_lo + lane; e < e_hi; e += 64) {
+      const int tau = pass == 0 ? e : pa[e];
+      const int d = 255 - ((tcnt[tau] >> (8 * pass)) & 255);
+      atomicAdd(wcnt + d * kSetupWaves + wave, 1);
+    }
+    __syncthreads();
+    setup_scan(wcnt, 256 * kSetupWaves, part, nullptr);
+    for (int e0 = e_lo; e0 < e_hi; e0 += 64) {
+      const int e = e0 + lane;
+      const bool valid = e < e_hi;
+      const int tau = !valid ? 0 : pass == 0 ? e : pa[e];
+      const int d = 255 - ((tcnt[tau] >> (8 * pass)) & 255);
+      unsigned long long m = __ballot(valid);               // the valid lanes of this lane's digit
+#pragma unroll
+      for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1;
+        const unsigned long long bal = __ballot(valid && bit);
+        m &= bit ? bal : ~bal;
+      }
+      const unsigned long long below = m & ((1ull << lane) - 1ull);
+      int* slot = wcnt + d * kSetupWaves + wave;              // this wave's next place for the digit
+      const int base = valid ? *slot : 0;
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if (valid) {
+        pb[base + __popcll(below)] = (unsigned short)tau;
+        if (below == 0ull) *slot = base + __popcll(m);
+      }
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+      __builtin_amdgcn_wave_barrier();
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+    __syncthreads();
+    unsigned short* t = pa;
+    pa = pb;
+    pb = t;
+  }
+  for (int t = tid; t < a.LT; t += kSetupThreads) a.torder[t] = npass ? pa[t] : t;
+  setup_scan(tcnt, a.LT + 1, part, a.pstart);
 }
 
 // ---------------------------------------------------------------------------------------
-// Pair stage.  blockIdx.y = objective; blockIdx.x < tau_blocks: T for kTauPerWg values of tau;
-// the blocks after them: Tm.
+// Pair list.  blockIdx.x < tau_blocks: the lists of kListWaves values of tau; the blocks after
+// them: Tm for every objective.
 //
-// One tau is one WAVE's (the waves of a workgroup share only the tables; after the tables are
-// staged there is no workgroup barrier, so the waves' memory round trips overlap): the pairs
-// (n <= m, c_n + c_m = tau) in (n ascending, m in bucket order) order -- lane l owns a contiguous
-// range of n, counts its pairs (the partner bucket is column tau - c_n, the m >= n of it), a wave
-// scan gives every n its place in the list -- written to the wave's LDS slice kPairChunk at a time
-// as (w_nm, table base of r_n + r_m).  The lanes over the rows then accumulate w E(2i - sigma) in
-// list order, kRowBlock rows per lane and list read (64 kRowBlock rows per pass over the list;
-// the running sums stay in registers across the chunks), with a compensated sum.
-// E table, split by parity so that consecutive rows read consecutive doubles:
+// One tau is one WAVE's: the pairs (n <= m, c_n + c_m = tau) in (n ascending, m in bucket order)
+// order -- lane l owns a contiguous range of n, counts its pairs (the partner bucket is column
+// tau - c_n, the m >= n of it), a wave scan gives every n its place in the list -- written to the
+// workspace at pstart[tau] as the table base of r_n + r_m (once) and w_nm (per objective; the
+// integer part of the list is the same for every objective).
+// E table of the accumulate kernel, split by parity so that consecutive rows read consecutive doubles:
 //   E(2i - sigma) = tabE[par * 2R + i + (s >> 1)],  s = 2R - 2 - sigma,  par = s & 1.
-// LDS: tabE[2][2R] | wl[waves][kPairChunk] | cstart[C + 1] | order[n] | rc[2n] | sl[waves][kPairChunk]
+// LDS: cstart[C + 1] | order[n] | rc[2n]
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kPairThreads) void conv_pair_kernel(const ConvArgs a, int tau_blocks) {
+__global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvArgs a, int tau_blocks) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
-  const int tid = threadIdx.x, o = blockIdx.y;
-  const double nhl = a.nhl[o], pv = a.pv[o];
+  const int tid = threadIdx.x;
   if ((int)blockIdx.x >= tau_blocks) {
     // Tm[o][n][i] = pv alpha_n H(i - r_n); rows n >= N are zero
     const long long total = (long long)a.NP * a.ldr;
-    const long long stride = (long long)(gridDim.x - tau_blocks) * kPairThreads;
-    double* tm = a.Tm + (size_t)o * a.NP * a.ldr;
-    for (long long t = (long long)(blockIdx.x - tau_blocks) * kPairThreads + tid; t < total; t += stride) {
-      const int n = (int)(t / a.ldr), i = (int)(t - (long long)n * a.ldr);
-      double v = 0.0;
-      if (n < a.n && i < a.nrows) {
-        const double d = (double)(a.row_lo + i - a.rc[2 * n]);
-        v = pv * a.alpha[(size_t)o * a.n_pad + n] * exp(nhl * (d * d));
+    const long long stride = (long long)(gridDim.x - tau_blocks) * (64 * kListWaves);
+    for (int o = 0; o < a.n_obj; ++o) {
+      const double nhl = a.nhl[o], pv = a.pv[o];
+      double* tm = a.Tm + (size_t)o * a.NP * a.ldr;
+      for (long long t = (long long)(blockIdx.x - tau_blocks) * (64 * kListWaves) + tid; t < total; t += stride) {
+        const int n = (int)(t / a.ldr), i = (int)(t - (long long)n * a.ldr);
+        double v = 0.0;
+        if (n < a.n && i < a.nrows) {
+          const double d = (double)(a.row_lo + i - a.rc[2 * n]);
+          v = pv * a.alpha[(size_t)o * a.n_pad + n] * exp(nhl * (d * d));
+        }
+        tm[t] = v;
       }
-      tm[t] = v;
     }
     return;
   }
-  extern __shared__ __attribute__((aligned(16))) double sd[];
-  const int R2 = 2 * a.R;
-  double* tabE = sd;
-  const int lane = tid & 63, wave = tid >> 6;
-  double* wl = tabE + 2 * R2 + wave * kPairChunk;
-  int* cstart = (int*)(tabE + 2 * R2 + kTauPerWg * kPairChunk);
+  extern __shared__ __attribute__((aligned(16))) int si[];
+  int* cstart = si;
   int* order = cstart + (a.C + 1);
   int* rc = order + a.n;
-  int* sl = rc + 2 * a.n + wave * kPairChunk;
-  for (int t = tid; t < 2 * R2; t += kPairThreads) {
-    const int par = t >= R2 ? 1 : 0, h = t - par * R2;
-    const double m = (double)(2 * h + par - (R2 - 2));
-    tabE[t] = exp(0.5 * nhl * (m * m));
-  }
-  for (int t = tid; t <= a.C; t += kPairThreads) cstart[t] = a.cstart[t];
-  for (int t = tid; t < a.n; t += kPairThreads) order[t] = a.order[t];
-  for (int t = tid; t < 2 * a.n; t += kPairThreads) rc[t] = a.rc[t];
+  for (int t = tid; t <= a.C; t += 64 * kListWaves) cstart[t] = a.cstart[t];
+  for (int t = tid; t < a.n; t += 64 * kListWaves) order[t] = a.order[t];
+  for (int t = tid; t < 2 * a.n; t += 64 * kListWaves) rc[t] = a.rc[t];
   __syncthreads();
-  const int tau = blockIdx.x * kTauPerWg + wave;
-  if (tau >= a.LT) return;
-  double* Trow = a.T + ((size_t)o * a.LT + tau) * a.ldr;
-  if (tau >= 2 * a.C - 1) {                           // the K padding of the contraction
-    for (int i = lane; i < a.ldr; i += 64) Trow[i] = 0.0;
-    return;
-  }
+  const int lane = tid & 63, wave = tid >> 6;
+  int* nm = rc + 2 * a.n + wave * kListChunk;          // the wave's slice: (n, m) in 16 + 16 bits
+  const int tau = blockIdx.x * kListWaves + wave;
+  if (tau >= 2 * a.C - 1) return;
+  const int p0 = __builtin_amdgcn_readfirstlane(a.pstart[tau]);
+  const int total = __builtin_amdgcn_readfirstlane(a.pstart[tau + 1]) - p0;
+  if (total == 0) return;
+  const int R2 = 2 * a.R;
   const int per = (a.n + 63) / 64;
   const int n_lo = lane * per < a.n ? lane * per : a.n;
   const int n_hi = n_lo + per < a.n ? n_lo + per : a.n;
-  const double* ko = a.kinv + (size_t)o * a.ld_k * a.ld_k;
   // this lane's pairs: for each n, the m >= n of column tau - c_n
   int mine = 0;
   for (int n = n_lo; n < n_hi; ++n) {
@@ -168,79 +291,170 @@ __global__ __launch_bounds__(kPairThreads) void conv_pair_kernel(const ConvArgs 
     const int v = __shfl_up(incl, d, 64);
     if (lane >= d) incl += v;
   }
-  const int total = __shfl(incl, 63, 64);
   const int first = incl - mine;
-  // (a shard of more than 64 kRowBlock = 1024 rows rebuilds the weight list -- K^-1 loads and exp --
-  // once per block of rows: the sums of a block stay in registers over the whole list instead.
-  // One block at C3; the cost gate counts the blocks)
-  for (int ib = 0; ib < a.ldr; ib += 64 * kRowBlock) {
-    // the row sums as unevaluated pairs hi + lo (two-sum and the product's FMA residual): the terms
-    // of one T entry cancel to 1e-4 .. 1e-5 of their magnitude (the conditioning of K), and a plain
-    // sum's partial sums would leave their rounding in T
-    double hi[kRowBlock], lo[kRowBlock];
-    int it[kRowBlock];
-#pragma unroll
-    for (int k = 0; k < kRowBlock; ++k) {
-      const int i = ib + lane + 64 * k;
-      // rows past the shard's (the padding to ldr) read a valid table entry and are dropped
-      it[k] = i < a.nrows ? i : a.nrows - 1;
-      hi[k] = 0.0;
-      lo[k] = 0.0;
-    }
-    for (int cb = 0; cb == 0 || cb < total; cb += kPairChunk) {
-      const int cnt = total - cb < kPairChunk ? total - cb : kPairChunk;
+  // kListChunk pairs at a time: the lanes that own them write (n, m) to the wave's slice in list
+  // order; then a lane per pair, so that the K^-1 loads of 64 pairs are in flight together and the
+  // list is written in whole lines
+  for (int cb = 0; cb < total; cb += kListChunk) {
+    const int cnt = total - cb < kListChunk ? total - cb : kListChunk;
+    if (first < cb + cnt && first + mine > cb) {
       int pos = first;
-      if (first < cb + cnt && first + mine > cb) {
-        for (int n = n_lo; n < n_hi; ++n) {
-          const int rn = rc[2 * n], cn = rc[2 * n + 1];
-          const int pc = tau - cn;
-          if (pc < 0 || pc >= a.C) continue;
-          for (int s = cstart[pc]; s < cstart[pc + 1]; ++s) {
-            const int m = order[s];
-            if (m < n) continue;
-            if (pos >= cb && pos < cb + cnt) {
-              const int rm = rc[2 * m];
-              const double dr = (double)(rn - rm), dc = (double)(cn - pc);
-              const double sym = m == n ? ko[(size_t)n * a.ld_k + n]
-                                        : ko[(size_t)n * a.ld_k + m] + ko[(size_t)m * a.ld_k + n];
-              // (2 - delta) A_nm = K^-1[n][m] + K^-1[m][n] off the diagonal; the library's exp
-              wl[pos - cb] = sym * (pv * pv) * exp(0.5 * nhl * (dr * dr + dc * dc));
-              const int sp = R2 - 2 - (rn + rm);
-              sl[pos - cb] = (sp & 1) * R2 + (sp >> 1) + a.row_lo;
-            }
-            ++pos;
-          }
+      for (int n = n_lo; n < n_hi; ++n) {
+        const int pc = tau - rc[2 * n + 1];
+        if (pc < 0 || pc >= a.C) continue;
+        for (int s = cstart[pc]; s < cstart[pc + 1]; ++s) {
+          const int m = order[s];
+          if (m < n) continue;
+          if (pos >= cb && pos < cb + cnt) nm[pos - cb] = n | (m << 16);
+          ++pos;
         }
       }
-      // the wave's own LDS slice: written by some lanes, read by all
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      for (int p = 0; p < cnt; ++p) {
-        const double w = wl[p];
-        const double* e = tabE + sl[p];
-#pragma unroll
-        for (int k = 0; k < kRowBlock; ++k) {
-          // (the rounded intrinsics keep the compiler from contracting the error-free forms)
-          const double ev = e[it[k]];
-          const double t = __dmul_rn(w, ev);
-          const double te = __builtin_fma(w, ev, -t);
-          const double s = __dadd_rn(hi[k], t);
-          const double bb = __dsub_rn(s, hi[k]);
-          const double se = __dadd_rn(__dsub_rn(hi[k], __dsub_rn(s, bb)), __dsub_rn(t, bb));
-          hi[k] = s;
-          lo[k] = __dadd_rn(lo[k], __dadd_rn(se, te));
-        }
+    }
+    // the wave's own LDS slice: written by some lanes, read by all
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    for (int p = lane; p < cnt; p += 64) {
+      const int n = nm[p] & 65535, m = nm[p] >> 16;
+      const int rn = rc[2 * n], cn = rc[2 * n + 1], rm = rc[2 * m];
+      const double dr = (double)(rn - rm), dc = (double)(cn - (tau - cn));
+      const int sp = R2 - 2 - (rn + rm);
+      a.pair_sl[p0 + cb + p] = (sp & 1) * R2 + (sp >> 1) + a.row_lo;
+      for (int o = 0; o < a.n_obj; ++o) {
+        const double* ko = a.kinv + (size_t)o * a.ld_k * a.ld_k;
+        const double nhl = a.nhl[o], pv = a.pv[o];
+        const double sym = m == n ? ko[(size_t)n * a.ld_k + n]
+                                  : ko[(size_t)n * a.ld_k + m] + ko[(size_t)m * a.ld_k + n];
+        // (2 - delta) A_nm = K^-1[n][m] + K^-1[m][n] off the diagonal; the library's exp
+        a.pair_w[(size_t)o * a.n_pairs + p0 + cb + p] = sym * (pv * pv) * exp(0.5 * nhl * (dr * dr + dc * dc));
       }
-      // the slice is rewritten by the next chunk
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
     }
+    // the slice is rewritten by the next chunk
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// ---------------------------------------------------------------------------------------
+// Accumulate.  blockIdx.y = objective.  A work item is (tau, block of kAccRows rows); item t of an
+// objective is row block t % nrb of tau torder[t / nrb], so the longest lists start first.
+// Persistent waves take the items through the objective's ticket (one lane's integer atomicAdd);
+// no wave waits for another.  A wave runs down its tau's list -- w and the table base are
+// wave-uniform loads -- and accumulates w E(2i - sigma) in list order, kAccRB rows per lane, with a
+// compensated sum.  A T entry is produced by one wave in list order: the ticket order is in no value.
+// LDS: tabE[2][2R]
+// ---------------------------------------------------------------------------------------
+// FULL: every row of the block is a row of the shard (the table offsets of the lane's rows are
+// immediates); else rows past the shard's (the padding to ldr) read a valid table entry and are
+// written as zero
+template <bool FULL>
+__device__ __forceinline__ void conv_acc_item(const double* tabE, const double* __restrict__ w,
+                                              const int* __restrict__ sl, int cnt, int ib, int lane, int nrows,
+                                              int ldr, double* __restrict__ Trow) {
+  // the row sums as unevaluated pairs hi + lo (two-sum and the product's FMA residual): the terms
+  // of one T entry cancel to 1e-4 .. 1e-5 of their magnitude (the conditioning of K), and a plain
+  // sum's partial sums would leave their rounding in T
+  double hi[kAccRB], lo[kAccRB];
+  int it[kAccRB];
 #pragma unroll
-    for (int k = 0; k < kRowBlock; ++k) {
-      const int i = ib + lane + 64 * k;
-      if (i < a.ldr) Trow[i] = i < a.nrows ? hi[k] + lo[k] : 0.0;
+  for (int k = 0; k < kAccRB; ++k) {
+    const int i = ib + lane + 64 * k;
+    it[k] = FULL ? 64 * k : (i < nrows ? i : nrows - 1);
+    hi[k] = 0.0;
+    lo[k] = 0.0;
+  }
+  const double* tb = FULL ? tabE + ib + lane : tabE;
+  auto gather = [&](int s, double (&ev)[kAccRB]) {
+    const double* e = tb + s;
+#pragma unroll
+    for (int k = 0; k < kAccRB; ++k) ev[k] = e[it[k]];
+  };
+  // the per-term operation sequence of the one-kernel pair stage, unchanged
+  auto term = [&](double wv, const double (&ev)[kAccRB]) {
+#pragma unroll
+    for (int k = 0; k < kAccRB; ++k) {
+      const double t = __dmul_rn(wv, ev[k]);
+      const double te = __builtin_fma(wv, ev[k], -t);
+      const double s2 = __dadd_rn(hi[k], t);
+      const double bb = __dsub_rn(s2, hi[k]);
+      const double se = __dadd_rn(__dsub_rn(hi[k], __dsub_rn(s2, bb)), __dsub_rn(t, bb));
+      hi[k] = s2;
+      lo[k] = __dadd_rn(lo[k], __dadd_rn(se, te));
     }
+  };
+  // kAccUnroll list entries per round: their (wave-uniform) loads go out together, and the table
+  // gathers of an entry are issued before the terms of the entry before it
+  int p = 0;
+  for (; p + kAccUnroll <= cnt; p += kAccUnroll) {
+    double wv[kAccUnroll];
+    int sv[kAccUnroll];
+#pragma unroll
+    for (int u = 0; u < kAccUnroll; ++u) {
+      wv[u] = w[p + u];
+      sv[u] = sl[p + u];
+    }
+    double ev[2][kAccRB];
+    gather(sv[0], ev[0]);
+#pragma unroll
+    for (int u = 0; u < kAccUnroll; ++u) {
+      if (u + 1 < kAccUnroll) gather(sv[u + 1], ev[(u + 1) & 1]);
+      term(wv[u], ev[u & 1]);
+    }
+  }
+  for (; p < cnt; ++p) {
+    double ev[kAccRB];
+    gather(sl[p], ev);
+    term(w[p], ev);
+  }
+#pragma unroll
+  for (int k = 0; k < kAccRB; ++k) {
+    const int i = ib + lane + 64 * k;
+    if (FULL) Trow[i] = hi[k] + lo[k];
+    else if (i < ldr) Trow[i] = i < nrows ? hi[k] + lo[k] : 0.0;
+  }
+}
+
+__global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs a, const double* __restrict__ pair_w,
+                                                                  const int* __restrict__ pair_sl,
+                                                                  const int* __restrict__ pstart,
+                                                                  const int* __restrict__ torder,
+                                                                  int* __restrict__ ticket, double* __restrict__ T,
+                                                                  int nrb, int ngrp, int dyn) {
+  if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
+  extern __shared__ __attribute__((aligned(16))) double sd[];
+  const int tid = threadIdx.x, lane = tid & 63, o = blockIdx.y;
+  const double nhl = a.nhl[o];
+  const int R2 = 2 * a.R;
+  double* tabE = sd;
+  for (int t = tid; t < 2 * R2; t += 64 * kAccWaves) {
+    const int par = t >= R2 ? 1 : 0, h = t - par * R2;
+    const double m = (double)(2 * h + par - (R2 - 2));
+    tabE[t] = exp(0.5 * nhl * (m * m));
+  }
+  __syncthreads();
+  const int n_items = a.LT * nrb;
+  const double* wo = pair_w + (size_t)o * a.n_pairs;
+  // group g = blockIdx.x % ngrp owns the items g, g + ngrp, ... and a ticket of its own; a wave's
+  // first item is its own index in the group (the setup kernel starts the tickets behind them)
+  const int g = blockIdx.x % ngrp;
+  int* tk = ticket + (o * kAccGroups + g) * kTicketStride;
+  for (int k = (blockIdx.x / ngrp) * kAccWaves + (tid >> 6);;) {
+    const int t = k * ngrp + g;
+    if (t >= n_items) break;
+    // the next ticket is taken before this item's work, which hides its round trip (the items at
+    // the end of the order, where a reserved item could be waited for, are the empty tau)
+    int nx = 0;
+    if (dyn && lane == 0) nx = atomicAdd(tk, 1);
+    const int oi = t / nrb, rb = t - oi * nrb;
+    const int tau = __builtin_amdgcn_readfirstlane(torder[oi]);
+    const int p0 = __builtin_amdgcn_readfirstlane(pstart[tau]);
+    const int cnt = __builtin_amdgcn_readfirstlane(pstart[tau + 1]) - p0;
+    const int ib = rb * kAccRows;
+    double* Trow = T + ((size_t)o * a.LT + tau) * a.ldr;
+    if (ib + kAccRows <= a.nrows) conv_acc_item<true>(tabE, wo + p0, pair_sl + p0, cnt, ib, lane, a.nrows, a.ldr, Trow);
+    else conv_acc_item<false>(tabE, wo + p0, pair_sl + p0, cnt, ib, lane, a.nrows, a.ldr, Trow);
+    if (!dyn) break;                       // no more items than waves: no tickets
+    k = __builtin_amdgcn_readfirstlane(nx);
   }
 }
 
@@ -514,20 +728,45 @@ static hipError_t conv_lds_attr(K k, size_t lds) {
   return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, hipStream_t st) {
-  const size_t l0 = conv_lds_setup(ca.n, ca.C), l1 = conv_lds_pair(ca.n, ca.R, ca.C),
-               l2 = conv_lds_contract(ca.n, ca.C);
+hipError_t launch_gridconv(const ConvArgs& ca, int grid, int cus, hipStream_t st) {
+  // The kernels' own LDS.  The plan's bounds dominate them: conv_lds_contract is about 48 C bytes, so
+  // C <= ~3400 (LT <= 6800), conv_lds_pair is 32 R + 24 KiB + ..., so R <= ~4300, and n <= 4096.  At
+  // those extremes setup needs 4 (3 C + 2 n) + 4 LT + 16.5 KiB = ~117 KiB, the list kernel
+  // 4 (C + 3 n) + 8 KiB = ~71 KiB, the accumulate kernel 32 R = ~135 KiB: all below 160 KiB, so the
+  // check below cannot fire for a planned call (it guards a future change of the plan's bounds)
+  const size_t l0 = ((size_t)ca.C + 1 + ca.n + kSetupWaves + (ca.LT + 1) + (ca.n < ca.C ? ca.n : ca.C) + 2 +
+                     256 * kSetupWaves) * sizeof(int) + (size_t)2 * ca.LT * sizeof(unsigned short);
+  const size_t l1 = ((size_t)(ca.C + 1) + 3 * (size_t)ca.n + kListWaves * kListChunk) * sizeof(int);
+  const size_t la = (size_t)4 * ca.R * sizeof(double);
+  const size_t l2 = conv_lds_contract(ca.n, ca.C);
+  if (l0 > kConvLdsBytes || l1 > kConvLdsBytes || la > kConvLdsBytes || ca.LT > 65536) return hipErrorInvalidValue;
   hipError_t e;
   if ((e = conv_lds_attr(conv_setup_kernel, l0)) != hipSuccess) return e;
-  if ((e = conv_lds_attr(conv_pair_kernel, l1)) != hipSuccess) return e;
+  if ((e = conv_lds_attr(conv_list_kernel, l1)) != hipSuccess) return e;
+  if ((e = conv_lds_attr(conv_acc_kernel, la)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_contract_kernel, l2)) != hipSuccess) return e;
-  hipLaunchKernelGGL(conv_setup_kernel, dim3(1), dim3(256), l0, st, ca);
+  // the accumulate kernel's persistent waves: up to 4 workgroups (4 waves per SIMD) per CU as the
+  // table's LDS allows, shared evenly by the objectives; no more waves than items
+  const int nrb = (ca.ldr + kAccRows - 1) / kAccRows;
+  const long long items = (long long)ca.LT * nrb;
+  const int per_cu = (int)(kConvLdsBytes / la < 4 ? kConvLdsBytes / la : 4);
+  long long wgs = (long long)(cus > 0 ? cus : 256) * per_cu / ca.n_obj;
+  if (wgs > (items + kAccWaves - 1) / kAccWaves) wgs = (items + kAccWaves - 1) / kAccWaves;
+  if (wgs < 1) wgs = 1;
+  const int ngrp = (int)(wgs < kAccGroups ? wgs : kAccGroups);
+  // tickets only when some wave has a second item: not when the groups are of equal size and hold
+  // no more items than waves (a wave's first item is its index in its group)
+  const int dyn = (items <= wgs * kAccWaves && wgs % ngrp == 0) ? 0 : 1;
+  hipLaunchKernelGGL(conv_setup_kernel, dim3(1), dim3(kSetupThreads), l0, st, ca, (int)wgs, ngrp, dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const int tau_blocks = (ca.LT + kTauPerWg - 1) / kTauPerWg;
+  const int tau_blocks = (2 * ca.C - 1 + kListWaves - 1) / kListWaves;
   const long long tm_elems = (long long)ca.NP * ca.ldr;
-  const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 256 ? (tm_elems + 1023) / 1024 : 256);
-  hipLaunchKernelGGL(conv_pair_kernel, dim3(tau_blocks + tm_blocks, ca.n_obj), dim3(kPairThreads), l1, st, ca,
-                     tau_blocks);
+  const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 512 ? (tm_elems + 1023) / 1024 : 512);
+  hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)wgs, ca.n_obj), dim3(64 * kAccWaves), la, st, ca,
+                     (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.torder,
+                     ca.ticket, ca.T, nrb, ngrp, dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(conv_contract_kernel, dim3(grid), dim3(256), l2, st, ca);
   return hipGetLastError();

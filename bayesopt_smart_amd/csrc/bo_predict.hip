@@ -548,9 +548,16 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
   const long long wgs = (n_wt + 3) / 4;
   pl->conv_grid = (int)(wgs < pl->grid ? wgs : pl->grid);
   pl->off_conv_ints = align256(pl->total);
-  pl->off_conv_Tm = pl->off_conv_ints + align256((size_t)(C + 1 + 3 * n) * sizeof(int));
+  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT + 1] | torder[LT] | tickets (a line each)
+  pl->off_conv_Tm = pl->off_conv_ints +
+                    align256((size_t)(C + 1 + 3 * n + 2 * pl->conv_LT + 1 + 32) * sizeof(int) +
+                             (size_t)BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride * sizeof(int));
   pl->off_conv_T = pl->off_conv_Tm + align256((size_t)d->n_obj * pl->conv_NP * pl->conv_ldr * sizeof(double));
-  pl->total = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
+  pl->off_conv_sl = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
+  // the pair list: every pair n <= m has one tau, so its length is known here
+  pl->conv_pairs = (int)(n * (n + 1) / 2);
+  pl->off_conv_w = pl->off_conv_sl + align256((size_t)pl->conv_pairs * sizeof(int));
+  pl->total = pl->off_conv_w + align256((size_t)d->n_obj * pl->conv_pairs * sizeof(double));
 }
 
 // Kernel choice and workspace layout of one call.
@@ -918,6 +925,12 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     ca.cstart = (int*)(ws + pl.off_conv_ints);
     ca.order = ca.cstart + (ca.C + 1);
     ca.rc = ca.order + ca.n;
+    ca.pstart = ca.rc + 2 * ca.n;
+    ca.torder = ca.pstart + (ca.LT + 1);
+    ca.ticket = (int*)(((uintptr_t)(ca.torder + ca.LT) + 127) & ~(uintptr_t)127);
+    ca.n_pairs = pl.conv_pairs;
+    ca.pair_sl = (int*)(ws + pl.off_conv_sl);
+    ca.pair_w = (double*)(ws + pl.off_conv_w);
     ca.Tm = (double*)(ws + pl.off_conv_Tm);
     ca.T = (double*)(ws + pl.off_conv_T);
     ca.mu = d->mu;
@@ -933,7 +946,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     ca.hkeys = fa.hkeys;
     ca.hidx = fa.hidx;
     ca.hmask = fa.hmask;
-    if (bo::launch_gridconv(ca, pl.conv_grid, s) != hipSuccess) return BO_ERR_HIP;
+    if (bo::launch_gridconv(ca, pl.conv_grid, num_cus(), s) != hipSuccess) return BO_ERR_HIP;
   }
   if (kmem) e = launch_kmem(pl, fa, s);
   else if (pl.fp32) switch (pl.dim_pad) {

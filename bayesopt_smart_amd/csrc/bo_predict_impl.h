@@ -93,6 +93,13 @@ struct ConvArgs {
   int* cstart;                           // [C + 1] first slot of each column's bucket
   int* order;                            // [n] training points sorted by column (stable)
   int* rc;                               // [n][2] integer coordinates (row, column)
+  int* pstart;                           // [LT + 1] first slot of each tau's pairs in the pair list
+  int* torder;                           // [LT] the tau by descending pair count, ties by ascending tau
+  int* ticket;                           // [BO_MAX_OBJ][kConvTicketGroups] (stride kConvTicketStride): the next
+                                         // work item of each group of the accumulate kernel's workgroups
+  int n_pairs;                           // n (n + 1) / 2: pairs n <= m, every one in exactly one tau
+  int* pair_sl;                          // [n_pairs] table base of r_n + r_m, tau-major list order
+  double* pair_w;                        // [n_obj][n_pairs] w_nm
   double* T;                             // [n_obj][LT][ldr]
   double* Tm;                            // [n_obj][NP][ldr]  pv alpha_n H(i - r_n)
   double *mu, *var, *std_mu, *std_var, *ucb, *acq;
@@ -105,11 +112,16 @@ struct ConvArgs {
   unsigned int hmask;
 };
 
-// LDS bytes of the three kernels; launch of the whole sequence (setup, pair stage, contraction)
+constexpr int kConvTicketGroups = 32;    // tickets per objective
+constexpr int kConvTicketStride = 32;    // ints between two tickets (one 128-byte line each)
+
+// LDS bounds that the plan tests (the pair stage's kernels launch with less than conv_lds_pair);
+// launch of the whole sequence (setup, pair list, accumulate, contraction): `grid` workgroups of
+// the contraction, `cus` compute units for the persistent accumulate kernel
 size_t conv_lds_setup(int n, int C);
 size_t conv_lds_pair(int n, int R, int C);
 size_t conv_lds_contract(int n, int C);
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, hipStream_t st);
+hipError_t launch_gridconv(const ConvArgs& ca, int grid, int cus, hipStream_t st);
 
 // Host-side plan of one bo_predict_acquire call (bo_predict.hip: make_plan).
 struct Plan {
@@ -132,7 +144,8 @@ struct Plan {
   bool conv;             // grid-convolution path planned (taken when the device flag allows)
   int conv_grid;         // its contraction kernel's workgroups (<= grid: it fills the same lists)
   int conv_row_lo, conv_nrows, conv_ldr, conv_LT, conv_NP, conv_Cpad;
-  size_t off_conv_T, off_conv_Tm, off_conv_ints;
+  size_t off_conv_T, off_conv_Tm, off_conv_ints, off_conv_sl, off_conv_w;
+  int conv_pairs;        // n (n + 1) / 2
 };
 
 // launch wrappers (one translation unit per padded dimension)
