@@ -56,6 +56,23 @@ class PredictDesc(C.Structure):
     ]
 
 
+class BucbDesc(C.Structure):
+    """Mirror of bo_bucb_desc (include/bo_amd.h)."""
+
+    _fields_ = [
+        ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
+        ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
+        ("cand_kind", C.c_int32), ("q", C.c_int32),
+        ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
+        ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
+        ("prior_var", C.c_double * MAX_OBJ), ("length_scale", C.c_double * MAX_OBJ),
+        ("beta", C.c_double * MAX_OBJ),
+        ("jitter", C.c_double), ("min_variance", C.c_double),
+        ("std_mu", c_vp), ("var", c_vp), ("ld", C.c_int64), ("mask", c_vp),
+        ("top_val", c_vp), ("top_idx", c_vp), ("var_out", c_vp), ("acq_out", c_vp),
+    ]
+
+
 class PowellResult(C.Structure):
     """Mirror of bo_powell_result (include/bo_amd.h)."""
 
@@ -116,6 +133,8 @@ _SIGS = {
     "bo_hvi_select_topq_masked": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, C.c_int32, c_dbl_p, c_dbl_p,
                                             c_vp, C.c_int64, C.c_int64, c_vp, C.c_int32, c_vp, c_vp, c_vp,
                                             C.c_size_t, c_vp]),
+    "bo_select_batch_bucb_workspace_size": (C.c_size_t, [C.POINTER(BucbDesc)]),
+    "bo_select_batch_bucb": (C.c_int, [C.POINTER(BucbDesc), c_vp, C.c_size_t, c_vp]),
     "bo_pareto_mask": (C.c_int, [c_vp, C.c_int64, C.c_int32, c_vp, c_vp]),
     "bo_hvi_boxes": (C.c_int, [c_dbl_p, C.c_int64, C.c_int32, c_dbl_p, c_vp, C.c_int64,
                                C.POINTER(C.c_int64)]),

@@ -275,6 +275,97 @@ def hvi_select_indices(acquisition_values, ucb, y_vector, n_evaluations, referen
     return idx[idx >= 0]
 
 
+BATCH_STRATEGIES = ("top", "bucb")
+
+
+def select_batch_bucb(std_mu_objectives, variance_objectives, x_train, kinv, cands, prior_variance,
+                      length_scales, betas, evaluated_points, batch_size, offset=0, count=None, mask=None,
+                      float_type=None, jitter=None, min_variance=None, return_variance=False,
+                      return_details=False):
+    """A batch whose later picks account for the earlier ones (GP-BUCB, Desautels, Krause &
+    Burdick 2014; bo_select_batch_bucb).  NOT in the reference: select_next_batch
+    (acquisition.py:116-144) takes the batch_size best values of one acquisition array, which on a
+    smooth posterior are neighbours of one maximum.  Here pick t is the best candidate of the
+    summed standardised UCB recomputed with the variance conditioned on picks 1..t-1 as
+    hallucinated observations (the mean does not change); the first pick is select_next_batch's.
+
+    std_mu_objectives / variance_objectives: the predict's outputs over the shard
+    [offset, offset + count) of `cands` (device [n_obj, >= count], not modified); x_train [N, d] and
+    kinv [n_obj, N, N] the fitted state the predict used.  `mask`: this shard's ExclusionMask,
+    updated here with evaluated_points (only the new rows are added); without one a mask is built
+    for the call.  jitter / min_variance default to KERNEL_JITTER / MIN_VARIANCE of `float_type`'s
+    branch (config.precision_constants).  One device call, no host synchronisation between the
+    picks.  Returns the global indices of the picks (fewer than batch_size when the shard runs out
+    of candidates) -- with `return_variance`, also the conditioned variance (device
+    [n_obj, count]); with `return_details`, a dict (top_idx, top_val, var, acq: device tensors)."""
+    from .config import precision_constants
+    if not 1 <= batch_size <= _lib.MAX_TOPQ:
+        raise ValueError(f"select_batch_bucb handles 1 <= batch_size <= {_lib.MAX_TOPQ}")
+    dev = _dev_of(std_mu_objectives, variance_objectives)
+    smu = _Arg(std_mu_objectives, dev)
+    var = _Arg(variance_objectives, dev)
+    n_obj = smu.t.shape[0]
+    count = int(cands.n - offset if count is None else count)
+    if smu.t.dim() != 2 or var.t.shape != smu.t.shape or smu.t.shape[1] < count or smu.t.stride(1) != 1 \
+            or var.t.stride() != smu.t.stride():
+        raise ValueError("std_mu / variance must be [n_obj, >= count] with one row stride")
+    x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
+    kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
+    n = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[0] != n_obj \
+            or kinv.shape[1] != kinv.shape[2] or kinv.shape[1] < n:
+        raise ValueError("x_train must be [N, d] and kinv [n_obj, >=N, >=N]")
+    kj, _, mv = precision_constants(float_type)
+    if mask is None:
+        mask = ExclusionMask(cands, offset, count, dev)
+    elif mask.offset != offset or mask.count != count:
+        raise ValueError("select_batch_bucb: the mask covers another shard")
+    mask.update(evaluated_points)
+    d = _lib.BucbDesc()
+    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.x_train, d.kinv, d.ld_k = x.data_ptr(), kinv.data_ptr(), kinv.shape[-1]
+    d.cand_kind, d.q = cands.kind_code, batch_size
+    d.n_cand, d.cand_offset = count, offset
+    if cands.kind == "grid":
+        for k in range(cands.dim):
+            d.grid_lo[k] = cands.lo[k]
+            d.grid_shape[k] = cands.shape[k]
+    elif cands.kind == "sobol":
+        d.cand = cands.cand_arg
+    else:                                              # explicit candidates: the shard's rows
+        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    for o in range(n_obj):
+        d.prior_var[o] = float(prior_variance[o])
+        d.length_scale[o] = float(length_scales[o])
+        d.beta[o] = float(betas[o])
+    d.jitter = float(kj if jitter is None else jitter)
+    d.min_variance = float(mv if min_variance is None else min_variance)
+    d.std_mu, d.var, d.ld = smu.ptr, var.ptr, smu.t.stride(0)
+    d.mask = mask.ptr
+    tv = torch.empty(batch_size, dtype=F64, device=dev)
+    ti = torch.empty(batch_size, dtype=torch.int64, device=dev)
+    d.top_val, d.top_idx = tv.data_ptr(), ti.data_ptr()
+    var_out = acq_out = None
+    if return_variance or return_details:
+        var_out = torch.empty_like(var.t)
+        d.var_out = var_out.data_ptr()
+    if return_details:
+        acq_out = torch.empty(count, dtype=F64, device=dev)
+        d.acq_out = acq_out.data_ptr()
+    lib = _lib.load()
+    nbytes = lib.bo_select_batch_bucb_workspace_size(d)
+    if nbytes == 0:
+        raise _lib.BoNativeError(_lib.ERR_ARG, "bo_select_batch_bucb_workspace_size")
+    ws = Workspace.get(nbytes, dev)
+    _lib.check(lib.bo_select_batch_bucb(d, ws.data_ptr(), ws.numel(), stream_handle(dev)),
+               "bo_select_batch_bucb")
+    if return_details:
+        return {"top_idx": ti, "top_val": tv, "var": var_out[:, :count], "acq": acq_out}
+    idx = ti.cpu().numpy()
+    idx = idx[idx >= 0].astype(np.int64)
+    return (idx, var_out[:, :count]) if return_variance else idx
+
+
 def update_hypervolume_improvement_exact(acquisition_values, ucb, y_vector, n_evaluations,
                                          reference_point, prior_mean, prior_variance):
     """The acquisition update of the loop (bayesian_optimization.py:195-199) as an exact HVI:

@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import ExclusionMask, hvi_select_indices, select_indices, update_hypervolume_improvement_exact
+from .acquisition import (BATCH_STRATEGIES, ExclusionMask, hvi_select_indices, select_batch_bucb, select_indices,
+                          update_hypervolume_improvement_exact)
 from .config import (DEFAULT_BATCH_SIZE, DEFAULT_BETA, DEFAULT_INITIAL_SAMPLES,
                      DEFAULT_LENGTH_SCALE, DEFAULT_PRIOR_MEAN, DEFAULT_PRIOR_VARIANCE,
                      resolve_float_type)
@@ -202,15 +203,30 @@ class DeviceBackend:
                 "std_var": b.std_variance_objectives, "ucb": b.ucb, "acq": b.acquisition_values}
 
     def select(self, fitted, prior_mean, prior_variance, length_scales, betas, batch_size, evaluated,
-               acquisition="sum_ucb", y_evaluated=None, reference_point=None):
+               acquisition="sum_ucb", y_evaluated=None, reference_point=None, batch_strategy="top"):
         """Global candidate indices of the next batch (select_next_batch's order, the evaluated
         points excluded).  "sum_ucb" is the reference's acquisition (acquisition.py:89-108, fused
         top-q); "hvi" replaces the acquisition array with the exact hypervolume improvement of the
-        UCB vectors over the Pareto front of `y_evaluated` above `reference_point`."""
+        UCB vectors over the Pareto front of `y_evaluated` above `reference_point`.
+        batch_strategy "top" is the reference's batch (the batch_size best values of one
+        acquisition array); "bucb" (not in the reference) takes every pick after the first from the
+        UCB recomputed with the variance conditioned on the earlier picks
+        (acquisition.select_batch_bucb), over this process's shard."""
         if acquisition not in ("sum_ucb", "hvi"):
             raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb' or 'hvi')")
+        _check_batch_strategy(batch_strategy, acquisition, batch_size, self.group)
         xd, yd, kinv = fitted
         out = self._outputs()
+        if batch_strategy == "bucb":
+            predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
+                            outputs=tuple(out), topq=0, offset=self.offset, count=self.count, out=out,
+                            device=self.dev, mode=self.mode, float_type=self.float_type)
+            if self._excl_mask is None:
+                self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
+            return select_batch_bucb(self.bufs.std_mu_objectives, self.bufs.variance_objectives, xd, kinv,
+                                     self.cands, prior_variance, length_scales, betas, evaluated, batch_size,
+                                     offset=self.offset, count=self.count, mask=self._excl_mask,
+                                     float_type=self.float_type)
         if acquisition == "sum_ucb" and batch_size <= _lib.MAX_TOPQ:
             from .distributed import sharded_predict_acquire
             _, (_, idx) = sharded_predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance,
@@ -264,7 +280,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
              n_objectives, function, betas, length_scales, batch_size, bounds,
              callbacks: Optional[List[Callable]] = None, *,
              acquisition: str = "sum_ucb", group=None, backend=None,
-             float_type=None) -> Tuple[np.ndarray, np.ndarray, int]:
+             float_type=None, batch_strategy: str = "top") -> Tuple[np.ndarray, np.ndarray, int]:
     """bayesian_optimization.py:51-247 with the reference's argument list.
 
     `kernel_matrices` and the posterior arrays may be HIP tensors (in place) or numpy arrays;
@@ -278,7 +294,9 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     filled (each rank holds its shard), the state dict's arrays are the gathered whole.  `group`
     selects the process group; `backend` replaces the device side (DeviceBackend's interface:
     fit / select / state_arrays / cands / rank / world / bufs).  `float_type` np.float32 runs the
-    reference's float32 branch (DeviceBackend).
+    reference's float32 branch (DeviceBackend).  `batch_strategy` "bucb" selects each batch by
+    hallucinated observations (DeviceBackend.select; one rank, acquisition "sum_ucb",
+    batch_size <= BO_MAX_TOPQ); "top", the default, is the reference's batch.
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -287,6 +305,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     del k_star, n_objectives, bounds  # unused, as in the reference (reference_point too, unless
     #                                   acquisition="hvi", the exact hypervolume improvement)
     n_obj = len(prior_mean)
+    _check_batch_strategy(batch_strategy, acquisition, batch_size, getattr(backend, "group", group))
     if backend is None:
         dev = require_device()
         cands = input_space if isinstance(input_space, CandidateSet) else CandidateSet.explicit(input_space, dev)
@@ -331,8 +350,11 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         optimized, fitted, t1 = backend.fit(x_vector, y_vector, current_eval, prior_mean, prior_variance,
                                             length_scales)
         t2 = time.perf_counter()
+        # the default strategy is not passed on: a caller's backend keeps the interface it has
+        strat = {} if batch_strategy == "top" else {"batch_strategy": batch_strategy}
         idx = backend.select(fitted, prior_mean, prior_variance, length_scales, betas, batch_size,
-                             x_vector[:current_eval], acquisition, y_vector[:current_eval], reference_point)
+                             x_vector[:current_eval], acquisition, y_vector[:current_eval], reference_point,
+                             **strat)
         x_next = cands.points(idx) if idx.size else np.zeros((0, cands.dim), dtype=np.int64)
         t3 = time.perf_counter()
         for b_idx, point in enumerate(x_next):
@@ -378,9 +400,27 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     return x_vector, y_vector, last_eval + 1
 
 
-def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb"):
+def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
+    """What batch_strategy="bucb" does not cover raises here, with the reason."""
+    if batch_strategy not in BATCH_STRATEGIES:
+        raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top' or 'bucb')")
+    if batch_strategy != "bucb":
+        return
+    if acquisition != "sum_ucb":
+        raise ValueError("batch_strategy='bucb' conditions the UCB acquisition ('sum_ucb'); it is not defined "
+                         f"for acquisition={acquisition!r}")
+    if batch_size > _lib.MAX_TOPQ:
+        raise ValueError(f"batch_strategy='bucb' supports batch_size <= {_lib.MAX_TOPQ} (got {batch_size})")
+    from .distributed import collectives_on
+    if collectives_on(group):
+        raise ValueError("batch_strategy='bucb' runs on one rank: with several, every pick would need an "
+                         "all-gather of the per-rank best candidates")
+
+
+def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", batch_strategy="top", group=None):
     """Fail in the constructor -- before any objective evaluation -- on shapes the device path
     cannot run (the reference would hit them only mid-loop, if at all)."""
+    _check_batch_strategy(batch_strategy, acquisition, batch_size, group)
     if not 1 <= n_obj <= _lib.MAX_OBJ:
         raise ValueError(f"n_objectives must be in [1, {_lib.MAX_OBJ}] (got {n_obj})")
     if acquisition == "hvi" and n_obj > 4:
@@ -413,7 +453,9 @@ class BayesianOptimization:
     of config.NUMBA_FLOAT_TYPE, or np.float32: the reference's float32 branch -- config.py:54-66
     jitters and variance floor, COBYLA for the fit, float32 host arrays -- with the predict on the
     f32 matrix cores) and ``initial_points`` ([n0, d] points evaluated as the initial design
-    instead of the Latin hypercube).
+    instead of the Latin hypercube) and ``batch_strategy`` ("top", the reference's batch: the
+    batch_size best acquisition values; or "bucb": every pick after the first accounts for the
+    earlier ones through hallucinated observations, acquisition.select_batch_bucb).
     With several ranks, each holds its shard of the posterior arrays, the initial design is drawn
     and evaluated on rank 0 (every rank draws the same RNG numbers, so the RNG stays in step) and
     broadcast, and the loop runs as `optimize` describes.
@@ -457,7 +499,9 @@ class BayesianOptimization:
         self.acquisition = kwargs.get("acquisition", "sum_ucb")
         if self.acquisition not in ("sum_ucb", "hvi"):
             raise ValueError(f"unknown acquisition {self.acquisition!r} (expected 'sum_ucb' or 'hvi')")
-        _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition)
+        self.batch_strategy = kwargs.get("batch_strategy", "top")
+        _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
+                      self.batch_strategy, self.group)
         self.x_vector = np.zeros((self.total_samples, self.dim), dtype=ft)
         self.y_vector = np.zeros((self.total_samples, n_objectives), dtype=ft)
         self._backend = DeviceBackend(self.candidates, n_objectives, self.total_samples, self.device,
@@ -518,7 +562,7 @@ class BayesianOptimization:
             betas=self.betas, length_scales=self.length_scales, batch_size=self.batch_size,
             bounds=self.bounds, callbacks=self.callbacks if self.callbacks else None,
             acquisition=self.acquisition, group=self.group, backend=self._backend,
-            float_type=self.float_type)
+            float_type=self.float_type, batch_strategy=self.batch_strategy)
 
     def pareto_analysis(self) -> np.ndarray:
         """bayesian_optimization.py:465-488."""

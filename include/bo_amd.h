@@ -241,6 +241,56 @@ int bo_select_topq_masked(const double* acq, int64_t n_cand, int64_t cand_offset
                           const uint32_t* mask, int32_t topq, double* top_val, int64_t* top_idx,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batch selection by hallucinated observations (GP-BUCB; Desautels, Krause & Burdick 2014).
+ * NOT in the reference: it extends select_next_batch (bayesopt/acquisition.py:116-144), whose
+ * batch is the q best values of ONE acquisition array (on a smooth posterior, q neighbours of
+ * one maximum).  Here pick t is the best candidate of the summed standardised UCB
+ *   acq_t[j] = sum_o std_mu_o[j] + beta_o sqrt(|var_o^(t-1)[j]| / pv_o)
+ * (select_next_batch's order: NaN first, descending value, ties by ascending global index;
+ * masked candidates and earlier picks skipped), after which every objective's variance is
+ * conditioned on an observation at that pick (the mean does not change):
+ *   c_t[j]   = cov0(j, p_t) - sum_{s<t} v_s[j] v_s[p_t],   cov0(j, p) = k(c_j, c_p) - k_j^T K^-1 k_p
+ *   d_t      = max(c_t[p_t], 0) + jitter,   v_t = c_t / sqrt(d_t)
+ *   var^t[j] = max(var^(t-1)[j] - v_t[j]^2, min_variance)     (unchanged when d_t is not finite)
+ * -- the posterior variance of a GP trained on X u {p_1..p_t} with `jitter` on every point.
+ * q = 1 is select_next_batch's top-1.  No host synchronisation between the picks: each one
+ * stays in device memory, the call is asynchronous on its stream and capturable in a HIP graph;
+ * deterministic (fixed-order reductions).  std_mu / var / mask are not modified.
+ * Fields shared with bo_predict_desc have its meaning; std_mu / var are that call's outputs. */
+typedef struct bo_bucb_desc {
+  int32_t n_obj;              /* objectives (<= BO_MAX_OBJ)                                   */
+  int32_t dim;                /* input dimensions (<= BO_MAX_DIM)                              */
+  int64_t n_train;            /* N >= 1                                                       */
+  const double* x_train;      /* device [n_train][dim]                                        */
+  const double* kinv;         /* device [n_obj][ld_k][ld_k]; leading N x N block = invert_k() */
+  int64_t ld_k;
+  int32_t cand_kind;          /* bo_cand_kind                                                 */
+  int32_t q;                  /* picks, 1 .. BO_MAX_TOPQ                                      */
+  const void* cand;           /* device [n_cand][dim] (kinds I64/F64); host bo_sobol_desc* (SOBOL) */
+  int64_t n_cand;             /* candidates of this call (a shard)                            */
+  int64_t cand_offset;        /* global index of this call's first candidate                  */
+  int64_t grid_lo[BO_MAX_DIM];     /* kind GRID                                              */
+  int64_t grid_shape[BO_MAX_DIM];  /* kind GRID (axis dim-1 fastest)                         */
+  double prior_var[BO_MAX_OBJ];
+  double length_scale[BO_MAX_OBJ];
+  double beta[BO_MAX_OBJ];
+  double jitter;              /* KERNEL_JITTER added by invert_k: 1e-6 (1e-3 float32 branch)  */
+  double min_variance;        /* MIN_VARIANCE: 1e-10 (1e-6 float32 branch)                    */
+  const double* std_mu;       /* device [n_obj][ld]: std_mu_objectives                        */
+  const double* var;          /* device [n_obj][ld]: variance_objectives (already floored)    */
+  int64_t ld;                 /* row stride of std_mu / var / var_out (>= n_cand)             */
+  const uint32_t* mask;       /* device, bo_excl_mask_update's layout over this shard; NULL = none */
+  double* top_val;            /* device [q]: acq_t[p_t] (-inf when no candidate is left)      */
+  int64_t* top_idx;           /* device [q]: global index of pick t, -1 = no candidate left   */
+  double* var_out;            /* optional device [n_obj][ld]: var^q                           */
+  double* acq_out;            /* optional device [n_cand]: the acquisition pick q was taken from */
+} bo_bucb_desc;
+/* bytes of device workspace bo_select_batch_bucb needs for `desc` (0 on bad args) */
+size_t bo_select_batch_bucb_workspace_size(const bo_bucb_desc* desc);
+int bo_select_batch_bucb(const bo_bucb_desc* desc, void* workspace, size_t workspace_bytes,
+                         void* stream);
+
 /* is_pareto_efficient  bayesopt/pareto.py:12-45: mask[i] = 1 iff no row j dominates row i
  * (maximisation, weak dominance; NaN rows never dominate nor are dominated).
  * y: device [n][n_obj] row-major; mask: device uint8 [n]. Bit-exact. */
