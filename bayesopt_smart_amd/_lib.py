@@ -24,7 +24,7 @@ OK, ERR_ARG, ERR_UNSUPPORTED, ERR_WORKSPACE, ERR_HIP, ERR_NOT_PD, ERR_SINGULAR =
 CAND_I64, CAND_F64, CAND_GRID, CAND_SOBOL = 0, 1, 2, 3
 ABI_VERSION = 5
 MODE_AUTO, MODE_DENSE, MODE_NO_SEPARABLE, MODE_FP32, MODE_F32_FLOOR = 0, 1, 2, 4, 8
-MODE_NO_GRID_CONV, MODE_GRID_CONV = 16, 32
+MODE_NO_GRID_CONV, MODE_GRID_CONV, MODE_GRID_CONV_FULL = 16, 32, 64
 
 c_dbl_p = C.POINTER(C.c_double)
 c_vp = C.c_void_p

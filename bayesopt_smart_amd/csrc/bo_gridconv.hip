@@ -20,11 +20,13 @@
 //   conv_setup_kernel     integer coordinates; training points bucketed by column (stable
 //                         counting sort); the pair stage's schedule: pairs per tau, their offsets
 //                         in the pair list, the tau by descending pair count, the tickets;
-//   conv_list_kernel      the pair list (one wave per tau): table base once, w_nm per objective;
-//                         and Tm[n][i] = pv alpha_n H(i - r_n);
+//   conv_list_kernel      the pair list (one wave per tau): table base once, w_nm per objective,
+//                         without the pairs that are negligible for every objective (kPairDrop);
+//                         and Tm[s][i] = pv alpha_n H(i - r_n), n = order[s];
 //   conv_acc_kernel       T: persistent waves take (tau, row block) items, longest lists first;
-//   conv_contract_kernel  the two GEMMs on v_mfma_f64_16x16x4_f64, the epilogue of
-//                         cm_predict_kernel, per-wave top-q lists in the TopEntry partial layout.
+//   conv_contract_kernel  the two GEMMs on v_mfma_f64_16x16x4_f64 over the k-blocks inside a tile's
+//                         band (kTabFlush), the epilogue of cm_predict_kernel, per-wave top-q lists
+//                         in the TopEntry partial layout.
 // No floating-point atomics (the tickets are integers and order work, not sums); every sum runs
 // in an order fixed by the inputs alone, and the K order of an output element does not depend on
 // its tile, so shards reproduce the single call.
@@ -57,6 +59,12 @@ constexpr int kAccGroups = bo::kConvTicketGroups;
 constexpr int kTicketStride = bo::kConvTicketStride;
 constexpr int kConvPF = 3;               // A-operand prefetch depth of the contraction (k-blocks)
 constexpr size_t kConvLdsBytes = 160 * 1024;
+// a pair whose |w_nm| is below kPairDrop pv for every objective is left out of the list: at most
+// N (N + 1) / 2 of them, so q / pv loses less than 1e-24 for N <= 4096
+constexpr double kPairDrop = 0x1p-100;
+// entries of the contraction's tables below kTabFlush are stored as +0.0: the k-blocks whose
+// entries are all zero for a tile add nothing to it and are not run
+constexpr double kTabFlush = 0x1p-128;
 
 // exclusive scan of v[0 .. len) in place over the workgroup, also written to out (if given);
 // part[kSetupWaves].  Contiguous segments per thread, a wave scan of their sums, the waves' totals.
@@ -232,7 +240,10 @@ __global__ __launch_bounds__(kSetupThreads) void conv_setup_kernel(const ConvArg
 // order -- lane l owns a contiguous range of n, counts its pairs (the partner bucket is column
 // tau - c_n, the m >= n of it), a wave scan gives every n its place in the list -- written to the
 // workspace at pstart[tau] as the table base of r_n + r_m (once) and w_nm (per objective; the
-// integer part of the list is the same for every objective).
+// integer part of the list is the same for every objective).  Only the pairs with |w_nm| >=
+// kPairDrop pv for some objective are written, closed up in unchanged order (a ballot per 64 pairs
+// and the wave's running count); pkept[tau] is their number (0 for an empty tau and for the padding
+// tau up to LT).  The criterion reads the call's inputs alone, so every shard keeps the same pairs.
 // E table of the accumulate kernel, split by parity so that consecutive rows read consecutive doubles:
 //   E(2i - sigma) = tabE[par * 2R + i + (s >> 1)],  s = 2R - 2 - sigma,  par = s & 1.
 // LDS: cstart[C + 1] | order[n] | rc[2n]
@@ -241,16 +252,17 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= tau_blocks) {
-    // Tm[o][n][i] = pv alpha_n H(i - r_n); rows n >= N are zero
+    // Tm[o][s][i] = pv alpha_n H(i - r_n), n = order[s]; rows s >= N are zero
     const long long total = (long long)a.NP * a.ldr;
     const long long stride = (long long)(gridDim.x - tau_blocks) * (64 * kListWaves);
     for (int o = 0; o < a.n_obj; ++o) {
       const double nhl = a.nhl[o], pv = a.pv[o];
       double* tm = a.Tm + (size_t)o * a.NP * a.ldr;
       for (long long t = (long long)(blockIdx.x - tau_blocks) * (64 * kListWaves) + tid; t < total; t += stride) {
-        const int n = (int)(t / a.ldr), i = (int)(t - (long long)n * a.ldr);
+        const int s = (int)(t / a.ldr), i = (int)(t - (long long)s * a.ldr);
         double v = 0.0;
-        if (n < a.n && i < a.nrows) {
+        if (s < a.n && i < a.nrows) {
+          const int n = a.order[s];                           // rows in column-bucketed order
           const double d = (double)(a.row_lo + i - a.rc[2 * n]);
           v = pv * a.alpha[(size_t)o * a.n_pad + n] * exp(nhl * (d * d));
         }
@@ -270,10 +282,13 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
   const int lane = tid & 63, wave = tid >> 6;
   int* nm = rc + 2 * a.n + wave * kListChunk;          // the wave's slice: (n, m) in 16 + 16 bits
   const int tau = blockIdx.x * kListWaves + wave;
-  if (tau >= 2 * a.C - 1) return;
+  if (tau >= a.LT) return;
   const int p0 = __builtin_amdgcn_readfirstlane(a.pstart[tau]);
   const int total = __builtin_amdgcn_readfirstlane(a.pstart[tau + 1]) - p0;
-  if (total == 0) return;
+  if (total == 0) {                                   // (the padding tau >= 2C - 1 among them)
+    if (lane == 0) a.pkept[tau] = 0;
+    return;
+  }
   const int R2 = 2 * a.R;
   const int per = (a.n + 63) / 64;
   const int n_lo = lane * per < a.n ? lane * per : a.n;
@@ -292,6 +307,7 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
     if (lane >= d) incl += v;
   }
   const int first = incl - mine;
+  int kept = 0;                                       // pairs of this tau written so far (wave-uniform)
   // kListChunk pairs at a time: the lanes that own them write (n, m) to the wave's slice in list
   // order; then a lane per pair, so that the K^-1 loads of 64 pairs are in flight together and the
   // list is written in whole lines
@@ -314,25 +330,49 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    for (int p = lane; p < cnt; p += 64) {
-      const int n = nm[p] & 65535, m = nm[p] >> 16;
-      const int rn = rc[2 * n], cn = rc[2 * n + 1], rm = rc[2 * m];
-      const double dr = (double)(rn - rm), dc = (double)(cn - (tau - cn));
-      const int sp = R2 - 2 - (rn + rm);
-      a.pair_sl[p0 + cb + p] = (sp & 1) * R2 + (sp >> 1) + a.row_lo;
-      for (int o = 0; o < a.n_obj; ++o) {
-        const double* ko = a.kinv + (size_t)o * a.ld_k * a.ld_k;
-        const double nhl = a.nhl[o], pv = a.pv[o];
-        const double sym = m == n ? ko[(size_t)n * a.ld_k + n]
-                                  : ko[(size_t)n * a.ld_k + m] + ko[(size_t)m * a.ld_k + n];
-        // (2 - delta) A_nm = K^-1[n][m] + K^-1[m][n] off the diagonal; the library's exp
-        a.pair_w[(size_t)o * a.n_pairs + p0 + cb + p] = sym * (pv * pv) * exp(0.5 * nhl * (dr * dr + dc * dc));
+    for (int pb = 0; pb < cnt; pb += 64) {
+      const int p = pb + lane;
+      // the objectives' weights in registers (the loop over BO_MAX_OBJ is unrolled: no indexed array)
+      double wv[BO_MAX_OBJ];
+      int sl = 0;
+      bool keep = false;
+      if (p < cnt) {
+        const int n = nm[p] & 65535, m = nm[p] >> 16;
+        const int rn = rc[2 * n], cn = rc[2 * n + 1], rm = rc[2 * m];
+        const double dr = (double)(rn - rm), dc = (double)(cn - (tau - cn));
+        const int sp = R2 - 2 - (rn + rm);
+        sl = (sp & 1) * R2 + (sp >> 1) + a.row_lo;
+#pragma unroll
+        for (int o = 0; o < BO_MAX_OBJ; ++o) {
+          if (o < a.n_obj) {
+            const double* ko = a.kinv + (size_t)o * a.ld_k * a.ld_k;
+            const double nhl = a.nhl[o], pv = a.pv[o];
+            const double sym = m == n ? ko[(size_t)n * a.ld_k + n]
+                                      : ko[(size_t)n * a.ld_k + m] + ko[(size_t)m * a.ld_k + n];
+            // (2 - delta) A_nm = K^-1[n][m] + K^-1[m][n] off the diagonal; the library's exp
+            wv[o] = sym * (pv * pv) * exp(0.5 * nhl * (dr * dr + dc * dc));
+            // a pair is dropped when it is negligible for every objective (the list is shared); a
+            // non-finite weight compares false and is kept
+            keep = keep || !(fabs(wv[o]) < kPairDrop * pv);
+          }
+        }
       }
+      // the kept pairs close up in list order: a lane's slot is the kept count before it
+      const unsigned long long kb = __ballot(keep);
+      if (keep) {
+        const int dst = p0 + kept + __popcll(kb & ((1ull << lane) - 1ull));
+        a.pair_sl[dst] = sl;
+#pragma unroll
+        for (int o = 0; o < BO_MAX_OBJ; ++o)
+          if (o < a.n_obj) a.pair_w[(size_t)o * a.n_pairs + dst] = wv[o];
+      }
+      kept += __popcll(kb);
     }
     // the slice is rewritten by the next chunk
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
+  if (lane == 0) a.pkept[tau] = kept;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -417,6 +457,7 @@ __device__ __forceinline__ void conv_acc_item(const double* tabE, const double* 
 __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs a, const double* __restrict__ pair_w,
                                                                   const int* __restrict__ pair_sl,
                                                                   const int* __restrict__ pstart,
+                                                                  const int* __restrict__ pkept,
                                                                   const int* __restrict__ torder,
                                                                   int* __restrict__ ticket, double* __restrict__ T,
                                                                   int nrb, int ngrp, int dyn) {
@@ -448,7 +489,7 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
     const int oi = t / nrb, rb = t - oi * nrb;
     const int tau = __builtin_amdgcn_readfirstlane(torder[oi]);
     const int p0 = __builtin_amdgcn_readfirstlane(pstart[tau]);
-    const int cnt = __builtin_amdgcn_readfirstlane(pstart[tau + 1]) - p0;
+    const int cnt = __builtin_amdgcn_readfirstlane(pkept[tau]);        // the pairs that the list kept
     const int ib = rb * kAccRows;
     double* Trow = T + ((size_t)o * a.LT + tau) * a.ldr;
     if (ib + kAccRows <= a.nrows) conv_acc_item<true>(tabE, wo + p0, pair_sl + p0, cnt, ib, lane, a.nrows, a.ldr, Trow);
@@ -467,8 +508,15 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
 //   B: MFMA step s pairs lane group g with k = k0 + 4g + s:
 //      variance  E(2j - tau) = tabB[par * HB + j + (u >> 1)], u = LT - 1 - tau, par = u & 1
 //                (split by parity: consecutive columns read consecutive doubles);
-//      mean      H(j - c_n)  = tabH[j - c_n + C - 1].
-// LDS: tabB[2][HB] | tabH[Cpad + C] | cn[NP]; rebuilt per objective.
+//      mean      H(j - c_n)  = tabH[j - c_n + C - 1]; the rows of Tm and cn[] are the training points
+//                in column-bucketed order (`order`), so the points near a tile are consecutive rows.
+// LDS: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] | cn[NP]; rebuilt per objective.
+// Bands: table entries below kTabFlush are stored as +0.0, and hband holds the largest |t| of an entry
+// that the same comparison kept (hq for E, hm for H).  A tile of columns j0 .. j0 + 63 runs
+//   variance  the k-blocks that hold a tau of [2 j0 - hq, 2 (j0 + 63) + hq],
+//   mean      the k-blocks that hold a row of cstart[j0 - hm] .. cstart[j0 + 64 + hm] - 1;
+// every other k-block multiplies finite T / Tm by exact zeros, and acc + 0 = acc: the outputs are those
+// of ConvArgs::full (every k-block), bit for bit, and do not depend on what a shard's tiles skipped.
 // The k-blocks ascend for every tile alike; the accumulators are read behind mfma_fence.
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void conv_load_a(const double* __restrict__ X, int ldr, int kb, int g, double (&v)[4]) {
@@ -478,7 +526,10 @@ __device__ __forceinline__ void conv_load_a(const double* __restrict__ X, int ld
 }
 
 // acc[nb] += X[k-blocks][rows] . B; bgen(kb, bv) fills bv[s][nb], this lane's B values of k-block kb
-// (k = 16 kb + 4 g + s, column block nb)
+// (k = 16 kb + 4 g + s, column block nb), for kb = 0 .. nkb - 1 in ascending order (nkb >= 1).  A band
+// that starts at k-block kb_lo passes X advanced by 16 kb_lo rows and a bgen whose base is moved by
+// as much: the first block is then in the pointers, not in a register that lives through the loop
+// (with one, the contraction kernel needed scratch)
 template <class BGen>
 __device__ __forceinline__ void conv_gemm(const double* __restrict__ X, int ldr, int nkb, int g, d4 (&acc)[4],
                                           BGen&& bgen) {
@@ -512,13 +563,15 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
   const int HB = a.Cpad + a.LT / 2;
   double* tabB = sd;
   double* tabH = tabB + 2 * HB;
+  // (the last entry of tabH's region is read by no tile: j - c_n + C - 1 <= Cpad + C - 2)
+  int* hband = (int*)(tabH + (a.Cpad + a.C - 1));                // [2] the bands of tabB and tabH: hq, hm
   int* cn = (int*)(tabH + (a.Cpad + a.C));
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, jl = lane & 15;
   const int cb_n = a.Cpad / 64;                                  // wave tiles along a grid row
   const long long n_wt = (long long)(a.ldr / 16) * cb_n;
   const long long gi_lo = a.cand_offset, gi_hi = a.cand_offset + a.n_cand;
-  for (int t = tid; t < a.NP; t += 256) cn[t] = t < a.n ? a.rc[2 * t + 1] : 0;
+  for (int t = tid; t < a.NP; t += 256) cn[t] = t < a.n ? a.rc[2 * a.order[t] + 1] : 0;
 
   double lv = -__builtin_inf();                                  // the wave's top-q list, lanes 0..q-1
   long long li = -1;
@@ -537,17 +590,51 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
       const double nhl = a.nhl[o];
       if (!(nhl == tab_nhl)) {
         __syncthreads();                                         // the previous tables are done with
+        // entries below kTabFlush become +0.0 (a NaN entry compares false and stays); the band is
+        // the largest |t| that the same comparison kept
+        int mq = 0;
         for (int t = tid; t < 2 * HB; t += 256) {
           const int par = t >= HB ? 1 : 0, h = t - par * HB;
-          const double m = (double)(2 * h + par - (a.LT - 1));
-          tabB[t] = exp(0.5 * nhl * (m * m));
+          const int mi = 2 * h + par - (a.LT - 1);
+          const double m = (double)mi;
+          const double v = exp(0.5 * nhl * (m * m));
+          const bool flush = v < kTabFlush;
+          tabB[t] = flush ? 0.0 : v;
+          if (!flush) mq = max(mq, abs(mi));
         }
-        for (int t = tid; t < a.Cpad + a.C; t += 256) {
-          const double m = (double)(t - (a.C - 1));
-          tabH[t] = exp(nhl * (m * m));
+        int mm = 0;
+        for (int t = tid; t < a.Cpad + a.C - 1; t += 256) {
+          const int mi = t - (a.C - 1);
+          const double m = (double)mi;
+          const double v = exp(nhl * (m * m));
+          const bool flush = v < kTabFlush;
+          tabH[t] = flush ? 0.0 : v;
+          if (!flush) mm = max(mm, abs(mi));
         }
+        if (tid < 2) hband[tid] = 0;
         __syncthreads();
+#pragma unroll
+        for (int d = 32; d > 0; d >>= 1) {
+          mq = max(mq, __shfl_xor(mq, d, 64));
+          mm = max(mm, __shfl_xor(mm, d, 64));
+        }
+        if (lane == 0) {
+          atomicMax(hband, mq);                                  // (integer maxima: no order in them)
+          atomicMax(hband + 1, mm);
+        }
+        __syncthreads();                                         // hband stays until the next build
         tab_nhl = nhl;
+      }
+      // variance k-blocks: those that hold a tau with E(2j - tau) != 0 for a column of the tile,
+      // tau in [2 j0 - hq, 2 (j0 + 63) + hq]; the others multiply T by exact zeros
+      int kq_lo = 0, kq_hi = a.LT / 16;
+      if (!a.full) {
+        const int hq = hband[0];                                 // largest |t| whose E(t) was not flushed
+        const int t_lo = 2 * j0 - hq > 0 ? 2 * j0 - hq : 0;
+        const int t_hi = 2 * (j0 + 63) + hq < a.LT - 1 ? 2 * (j0 + 63) + hq : a.LT - 1;
+        // (wave-uniform, and told so: as lane values they made the k loop a divergent one)
+        kq_lo = __builtin_amdgcn_readfirstlane(t_lo >> 4);
+        kq_hi = __builtin_amdgcn_readfirstlane((t_hi >> 4) + 1);
       }
       d4 aq[4], am[4];
 #pragma unroll
@@ -555,13 +642,23 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
         aq[nb] = (d4){0.0, 0.0, 0.0, 0.0};
         am[nb] = (d4){0.0, 0.0, 0.0, 0.0};
       }
-      const double* Tq = a.T + (size_t)o * a.LT * a.ldr + i0 + jl;
-      const double* Tm = a.Tm + (size_t)o * a.NP * a.ldr + i0 + jl;
-      // variance: step s of lane group g is tau = 16 kb + 4 g + s; u = LT - 1 - tau is odd for even
-      // s, and u >> 1 = hb (s = 0, 1) or hb - 1 (s = 2, 3), hb = LT/2 - 1 - 8 kb - 2 g  (>= 1)
-      conv_gemm(Tq, a.ldr, a.LT / 16, g, aq, [&](int kb, double (&bv)[4][4]) {
-        const int hb = a.LT / 2 - 1 - 8 * kb - 2 * g;
-        const double* pe = tabB + hb + j0 + jl;                  // even u
+      const double* Tq = a.T + ((size_t)o * a.LT + 16 * kq_lo) * a.ldr + i0 + jl;
+      // mean k-blocks: the rows are in column order, so the points of the columns
+      // [j0 - hm, j0 + 63 + hm] are the rows cstart[..] .. cstart[..] - 1; H is zero for the others
+      int km_lo = 0, km_hi = a.NP / 16;
+      if (!a.full) {
+        const int hm = hband[1];
+        const int c_lo = j0 - hm > 0 ? j0 - hm : 0, c_hi = j0 + 64 + hm < a.C ? j0 + 64 + hm : a.C;
+        km_lo = __builtin_amdgcn_readfirstlane(a.cstart[c_lo] >> 4);
+        km_hi = __builtin_amdgcn_readfirstlane((a.cstart[c_hi] + 15) >> 4);
+      }
+      const double* Tm = a.Tm + ((size_t)o * a.NP + 16 * km_lo) * a.ldr + i0 + jl;
+      // variance: step s of lane group g is tau = 16 (kq_lo + kb) + 4 g + s; u = LT - 1 - tau is odd
+      // for even s, and u >> 1 = hb (s = 0, 1) or hb - 1 (s = 2, 3), hb = LT/2 - 1 - 8 (kq_lo + kb) - 2 g
+      // (>= 1)
+      const double* pe0 = tabB + (a.LT / 2 - 1 - 8 * kq_lo - 2 * g) + j0 + jl;
+      conv_gemm(Tq, a.ldr, kq_hi - kq_lo, g, aq, [&](int kb, double (&bv)[4][4]) {
+        const double* pe = pe0 - 8 * kb;                         // even u
         const double* po = pe + HB;                              // odd u
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
@@ -571,8 +668,9 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
           bv[3][nb] = pe[16 * nb - 1];
         }
       });
-      conv_gemm(Tm, a.ldr, a.NP / 16, g, am, [&](int kb, double (&bv)[4][4]) {
-        const int* c4 = cn + 16 * kb + 4 * g;
+      const int* cn0 = cn + 16 * km_lo + 4 * g;
+      if (km_hi > km_lo) conv_gemm(Tm, a.ldr, km_hi - km_lo, g, am, [&](int kb, double (&bv)[4][4]) {
+        const int* c4 = cn0 + 16 * kb;
         const double* ph = tabH + j0 + jl + (a.C - 1);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -759,13 +857,14 @@ hipError_t launch_gridconv(const ConvArgs& ca, int grid, int cus, hipStream_t st
   const int dyn = (items <= wgs * kAccWaves && wgs % ngrp == 0) ? 0 : 1;
   hipLaunchKernelGGL(conv_setup_kernel, dim3(1), dim3(kSetupThreads), l0, st, ca, (int)wgs, ngrp, dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const int tau_blocks = (2 * ca.C - 1 + kListWaves - 1) / kListWaves;
+  const int tau_blocks = (ca.LT + kListWaves - 1) / kListWaves;    // the padding tau too: their pkept
   const long long tm_elems = (long long)ca.NP * ca.ldr;
   const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 512 ? (tm_elems + 1023) / 1024 : 512);
   hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)wgs, ca.n_obj), dim3(64 * kAccWaves), la, st, ca,
-                     (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.torder,
+                     (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.pkept,
+                     (const int*)ca.torder,
                      ca.ticket, ca.T, nrb, ngrp, dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(conv_contract_kernel, dim3(grid), dim3(256), l2, st, ca);

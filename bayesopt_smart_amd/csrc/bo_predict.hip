@@ -504,8 +504,9 @@ int num_cus() {
 //     old  = 25 + (rounds of 256 tiles of 64 candidates) x 64 x (F / 273e3 + 0.038),
 //            F = n_obj 1024 nch (nch + 1) MFMA flops per candidate at the measured 70 TF.
 //   Both sides reproduce the 15 measured points within 20 %; the margin covers that.
-//   BO_PREDICT_GRID_CONV skips the gate, BO_PREDICT_NO_GRID_CONV and BO_GRID_CONV=0 (environment,
-//   read here: fixed when a graph is captured) never plan it.
+//   BO_PREDICT_GRID_CONV skips the gate (so does BO_PREDICT_GRID_CONV_FULL, which also runs every
+//   k-block of the contraction), BO_PREDICT_NO_GRID_CONV and BO_GRID_CONV=0 (environment, read here:
+//   fixed when a graph is captured) never plan it.
 constexpr double kConvMargin = 1.15;
 constexpr int kConvMaxN = 4096;          // conv_setup_kernel ranks a point against all earlier ones
 
@@ -522,7 +523,7 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
     return;
   const long long row_lo = d->cand_offset / C, row_hi = (d->cand_offset + d->n_cand - 1) / C;
   const long long nrows = row_hi - row_lo + 1;
-  if (!(d->mode & BO_PREDICT_GRID_CONV)) {
+  if (!(d->mode & (BO_PREDICT_GRID_CONV | BO_PREDICT_GRID_CONV_FULL))) {
     const double nch = pl->n_pad / 32;
     const double F = (double)d->n_obj * 1024.0 * nch * (nch + 1);
     const double old_rounds = (double)(((d->n_cand + 63) / 64 + 255) / 256);
@@ -548,9 +549,9 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
   const long long wgs = (n_wt + 3) / 4;
   pl->conv_grid = (int)(wgs < pl->grid ? wgs : pl->grid);
   pl->off_conv_ints = align256(pl->total);
-  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT + 1] | torder[LT] | tickets (a line each)
+  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT + 1] | torder[LT] | pkept[LT] | tickets (a line each)
   pl->off_conv_Tm = pl->off_conv_ints +
-                    align256((size_t)(C + 1 + 3 * n + 2 * pl->conv_LT + 1 + 32) * sizeof(int) +
+                    align256((size_t)(C + 1 + 3 * n + 3 * pl->conv_LT + 1 + 32) * sizeof(int) +
                              (size_t)BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride * sizeof(int));
   pl->off_conv_T = pl->off_conv_Tm + align256((size_t)d->n_obj * pl->conv_NP * pl->conv_ldr * sizeof(double));
   pl->off_conv_sl = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
@@ -574,7 +575,7 @@ int make_plan(const bo_predict_desc* d, Plan* pl, bool query_device, bool kmem =
   if (d->n_train < 1 || d->n_cand < 0 || d->topq < 0 || d->topq > BO_MAX_TOPQ) return BO_ERR_ARG;
   if (d->cand_kind < 0 || d->cand_kind > BO_CAND_SOBOL) return BO_ERR_ARG;
   if (d->mode & ~(BO_PREDICT_DENSE | BO_PREDICT_NO_SEPARABLE | BO_PREDICT_FP32 | BO_PREDICT_F32_FLOOR |
-                  BO_PREDICT_NO_GRID_CONV | BO_PREDICT_GRID_CONV))
+                  BO_PREDICT_NO_GRID_CONV | BO_PREDICT_GRID_CONV | BO_PREDICT_GRID_CONV_FULL))
     return BO_ERR_ARG;
   if (d->excl_points && d->n_excl < 0) return BO_ERR_ARG;
   const long long n = d->n_train;
@@ -927,7 +928,9 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     ca.rc = ca.order + ca.n;
     ca.pstart = ca.rc + 2 * ca.n;
     ca.torder = ca.pstart + (ca.LT + 1);
-    ca.ticket = (int*)(((uintptr_t)(ca.torder + ca.LT) + 127) & ~(uintptr_t)127);
+    ca.pkept = ca.torder + ca.LT;
+    ca.ticket = (int*)(((uintptr_t)(ca.pkept + ca.LT) + 127) & ~(uintptr_t)127);
+    ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
     ca.n_pairs = pl.conv_pairs;
     ca.pair_sl = (int*)(ws + pl.off_conv_sl);
     ca.pair_w = (double*)(ws + pl.off_conv_w);

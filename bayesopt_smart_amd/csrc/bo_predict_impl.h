@@ -94,6 +94,8 @@ struct ConvArgs {
   int* order;                            // [n] training points sorted by column (stable)
   int* rc;                               // [n][2] integer coordinates (row, column)
   int* pstart;                           // [LT + 1] first slot of each tau's pairs in the pair list
+  int* pkept;                            // [LT] pairs of each tau that the list kept (|w| >= 2^-100 pv for some
+                                         // objective), compacted at pstart[tau]
   int* torder;                           // [LT] the tau by descending pair count, ties by ascending tau
   int* ticket;                           // [BO_MAX_OBJ][kConvTicketGroups] (stride kConvTicketStride): the next
                                          // work item of each group of the accumulate kernel's workgroups
@@ -101,9 +103,10 @@ struct ConvArgs {
   int* pair_sl;                          // [n_pairs] table base of r_n + r_m, tau-major list order
   double* pair_w;                        // [n_obj][n_pairs] w_nm
   double* T;                             // [n_obj][LT][ldr]
-  double* Tm;                            // [n_obj][NP][ldr]  pv alpha_n H(i - r_n)
+  double* Tm;                            // [n_obj][NP][ldr]  pv alpha_n H(i - r_n), row s is n = order[s]
   double *mu, *var, *std_mu, *std_var, *ucb, *acq;
   int topq;
+  int full;                              // BO_PREDICT_GRID_CONV_FULL: every k-block of both GEMMs
   TopEntry* partial;                     // [n_lists][topq]
   int n_lists;                           // lists the merge reads (those past the grid's are emptied)
   const double* excl_pts;                // rows the hash set indexes ([*][2])

@@ -165,7 +165,8 @@ def _fill_desc(x_train, y_train, kinv, cands, pm, pv, ls, betas, offset, count, 
 
 
 MODES = {"auto": 0, "dense": 1, "auto-exp": 2, "dense-exp": 3, "fp32": 4,
-         "auto-noconv": _lib.MODE_NO_GRID_CONV, "auto-conv": _lib.MODE_GRID_CONV}
+         "auto-noconv": _lib.MODE_NO_GRID_CONV, "auto-conv": _lib.MODE_GRID_CONV,
+         "auto-conv-full": _lib.MODE_GRID_CONV_FULL}
 
 
 def predict_acquire(x_train, y_train, kinv, cands: CandidateSet, prior_mean, prior_variance,
@@ -185,7 +186,9 @@ def predict_acquire(x_train, y_train, kinv, cands: CandidateSet, prior_mean, pri
     (checked on the device) "auto" takes the grid-convolution path when the plan's cost gate expects
     it to be faster: the same quadratic form regrouped over the midpoints of the training pairs,
     q(i, j) = sum_tau T(i, tau) E(2j - tau); "auto-conv" takes it whenever the shape
-    allows, "auto-noconv" (or BO_GRID_CONV=0 in the environment) never.  The "-exp" modes disable the integer-grid
+    allows, "auto-noconv" (or BO_GRID_CONV=0 in the environment) never; "auto-conv-full" is "auto-conv"
+    without the band of the contraction (every k-block is run: bit for bit the same outputs, the
+    reference mode of the band's tests).  The "-exp" modes disable the integer-grid
     separable K* generation (exp table) and evaluate every K* entry with exp().  "fp32" runs
     K* and the upper-form contraction in f32 on the f32 matrix cores (BASELINE config C5) and
     everything after the mean / quadratic form in f64.

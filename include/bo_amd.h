@@ -107,7 +107,18 @@ int bo_device_count(void);
  * pairs, q(i, j) = sum_tau T(i, tau) E(2j - tau), 2 (2C - 1) + 2N matrix-core flops per candidate
  * and objective instead of N^2.  Planned when a cost gate passes; BO_PREDICT_GRID_CONV plans it
  * whenever the shape allows, BO_PREDICT_NO_GRID_CONV (or BO_GRID_CONV=0 in the environment)
- * never.  When the device check fails the call runs the chunk-major kernel as before. */
+ * never.  When the device check fails the call runs the chunk-major kernel as before.
+ * The path leaves out what cannot reach the result: training pairs with |w_nm| < 2^-100 pv for
+ * every objective (q / pv loses less than 1e-24 for N <= 4096), and the k-blocks of the two
+ * contractions in which E(2j - tau) < 2^-128 (variance) or H(j - c_n) < 2^-128 (mean) for every
+ * column of a 64-column tile (the tables store such entries as +0.0, so a skipped block would
+ * have added exact zeros).
+ * BO_PREDICT_GRID_CONV_FULL plans the path like BO_PREDICT_GRID_CONV and runs every k-block over
+ * the same tables and the same pair list: its outputs are bit for bit those of the banded run
+ * whenever K^-1 and alpha are finite (the reference mode of the band's tests).  A non-finite
+ * K^-1 entry or alpha_n spreads NaN only to the candidates inside the band around its pair's
+ * midpoint column (its point's column), not along the whole grid row as 0 * NaN does where every
+ * k-block is run; with BO_PREDICT_GRID_CONV_FULL it still reaches every column. */
 typedef enum bo_predict_mode {
   BO_PREDICT_AUTO = 0,
   BO_PREDICT_DENSE = 1,
@@ -115,7 +126,8 @@ typedef enum bo_predict_mode {
   BO_PREDICT_FP32 = 4,
   BO_PREDICT_F32_FLOOR = 8,
   BO_PREDICT_NO_GRID_CONV = 16,
-  BO_PREDICT_GRID_CONV = 32
+  BO_PREDICT_GRID_CONV = 32,
+  BO_PREDICT_GRID_CONV_FULL = 64
 } bo_predict_mode;
 
 typedef struct bo_predict_desc {
