@@ -15,15 +15,17 @@
 // the same N^2 products as k' K^-1 k (update_variance, numba_kernels.py:491-535), grouped so that
 // a candidate costs 2 (2C - 1) + 2 N matrix-core flops per objective instead of N^2.
 //
-// Four launches, each returning at once unless the device flag (predict_prep_kernel) says that
-// every training point is a grid point:
-//   conv_setup_kernel     integer coordinates; training points bucketed by column (stable
-//                         counting sort); the pair stage's schedule: pairs per tau, their offsets
-//                         in the pair list, the tau by descending pair count, the tickets;
-//   conv_list_kernel      the pair list (one wave per tau): table base once, w_nm per objective,
-//                         without the pairs that are negligible for every objective (kPairDrop);
+// The setup is a role block of the prep launch (conv_setup_block, bo_predict_impl.h): integer
+// coordinates; training points bucketed by column (stable counting sort); the tickets' start values,
+// the class counters zeroed.  Then three launches, each returning at once unless the device flag
+// (predict_prep_kernel) says that every training point is a grid point:
+//   conv_list_kernel      the pair list (one wave per tau): its offset from the column buckets in
+//                         closed form, table base once, w_nm per objective, without the pairs that
+//                         are negligible for every objective (kPairDrop); the tau appended to the
+//                         list of its class of kept pairs, or its T rows zeroed when it kept none;
 //                         and Tm[s][i] = pv alpha_n H(i - r_n), n = order[s];
-//   conv_acc_kernel       T: persistent waves take (tau, row block) items, longest lists first;
+//   conv_acc_kernel       T: persistent waves take (tau, row block) items from the class lists,
+//                         the class of the longest lists first;
 //   conv_contract_kernel  the two GEMMs on v_mfma_f64_16x16x4_f64 over the k-blocks inside a tile's
 //                         band (kTabFlush), the epilogue of cm_predict_kernel, per-wave top-q lists
 //                         in the TopEntry partial layout.
@@ -40,11 +42,9 @@ using bo::ConvArgs;
 // the LDS layout of the removed one-kernel pair stage, kept for conv_lds_pair alone (the plan's gate)
 constexpr int kPairChunk = 256;
 constexpr int kTauPerWg = 8;
-constexpr int kSetupThreads = 1024;
-constexpr int kSetupWaves = kSetupThreads / 64;
 constexpr int kListWaves = 4;            // waves per workgroup of the list kernel, one tau each
 constexpr int kListChunk = 512;          // pairs of one tau staged in LDS at a time (per wave)
-constexpr int kAccWaves = 4;             // waves per workgroup of the accumulate kernel
+constexpr int kAccWaves = bo::kConvAccWaves;   // waves per workgroup of the accumulate kernel
 // rows per lane of a work item.  BO_BUILD_VARIANT=DEF_ACC_RB=16 builds the other candidate (A/B in
 // DESIGN.md §9)
 #ifndef BO_ACC_RB
@@ -57,6 +57,15 @@ constexpr int kAccUnroll = 4;            // list entries loaded ahead of their t
 // as long as its atomics: ~25 ns each on one address from 8 XCDs, 6,000 of them at C3 (160 us)
 constexpr int kAccGroups = bo::kConvTicketGroups;
 constexpr int kTicketStride = bo::kConvTicketStride;
+// the work order of the accumulate kernel: the tau that kept pairs, appended by their list waves to
+// the list of their class (half-octaves of the kept count) and shard (tau % kShards: 400 to 630 tau
+// share a class at C3, and their atomics on one address would queue)
+constexpr int kClasses = bo::kConvClasses;
+constexpr int kShards = bo::kConvShards;
+constexpr int kCountStride = bo::kConvCountStride;
+constexpr int kClassLists = kClasses * kShards;
+static_assert(kClassLists % 64 == 0 && kClassLists <= 2 * 64 * kAccWaves && (kShards & (kShards - 1)) == 0 &&
+              kShards <= 16 && kShards <= kCountStride, "conv_acc_kernel's scan and lookup of the class lists");
 constexpr int kConvPF = 3;               // A-operand prefetch depth of the contraction (k-blocks)
 constexpr size_t kConvLdsBytes = 160 * 1024;
 // a pair whose |w_nm| is below kPairDrop pv for every objective is left out of the list: at most
@@ -66,172 +75,6 @@ constexpr double kPairDrop = 0x1p-100;
 // entries are all zero for a tile add nothing to it and are not run
 constexpr double kTabFlush = 0x1p-128;
 
-// exclusive scan of v[0 .. len) in place over the workgroup, also written to out (if given);
-// part[kSetupWaves].  Contiguous segments per thread, a wave scan of their sums, the waves' totals.
-__device__ __forceinline__ void setup_scan(int* v, int len, int* part, int* out) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int seg = (len + kSetupThreads - 1) / kSetupThreads;
-  const int c_lo = tid * seg < len ? tid * seg : len, c_hi = c_lo + seg < len ? c_lo + seg : len;
-  int sum = 0;
-  for (int c = c_lo; c < c_hi; ++c) sum += v[c];
-  int incl = sum;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int t = __shfl_up(incl, d, 64);
-    if (lane >= d) incl += t;
-  }
-  if (lane == 63) part[wave] = incl;
-  __syncthreads();
-  int run = incl - sum;
-  for (int w = 0; w < wave; ++w) run += part[w];
-  for (int c = c_lo; c < c_hi; ++c) {
-    const int t = v[c];
-    v[c] = run;
-    if (out) out[c] = run;
-    run += t;
-  }
-  __syncthreads();
-}
-
-// ---------------------------------------------------------------------------------------
-// Setup: rc[n] = integer (row, column) of training point n; cstart / order = the points bucketed
-// by column, ascending n inside a bucket; and the schedule of the pair stage: pstart[tau] = first
-// slot of tau's pairs in the pair list (tau's count = pstart[tau + 1] - pstart[tau]), torder = the
-// tau by descending pair count (ties by ascending tau), the accumulate kernel's tickets.
-// One workgroup.
-//   pairs per tau: every pair of non-empty columns c <= c' adds h[c] h[c'] (c < c') or
-//   h[c] (h[c] + 1) / 2 (c = c') to tau = c + c' (integer atomics in LDS);
-//   work order: a stable radix sort of the tau (ascending at the start) by 255 - digit, 8 bits a
-//   pass, as many passes as the largest count has digits (one at C3).  A wave owns a contiguous
-//   chunk of the sequence: per-(digit, wave) counts, one scan in (digit, wave) order, then the
-//   wave places its chunk 64 entries at a time (the lanes of equal digit found by 8 ballots keep
-//   their order).
-// LDS: cnt[C + 1] | col[n] | part[waves] | tcnt[LT + 1] | clist[min(n, C)] | nnz, max |
-//      wcnt[256][waves] | perm[2][LT] (16 bits each)
-// ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kSetupThreads) void conv_setup_kernel(const ConvArgs a, int acc_wgs, int ngrp, int dyn) {
-  if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
-  extern __shared__ __attribute__((aligned(16))) int si[];
-  int* cnt = si;
-  int* col = cnt + (a.C + 1);
-  int* part = col + a.n;
-  int* tcnt = part + kSetupWaves;
-  int* clist = tcnt + (a.LT + 1);
-  int* misc = clist + (a.n < a.C ? a.n : a.C);
-  int* wcnt = misc + 2;
-  unsigned short* perm = (unsigned short*)(wcnt + 256 * kSetupWaves);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  for (int c = tid; c <= a.C; c += kSetupThreads) cnt[c] = 0;
-  for (int t = tid; t <= a.LT; t += kSetupThreads) tcnt[t] = 0;
-  if (tid < 2) misc[tid] = 0;
-  // the first items of the accumulate kernel's waves are their own indices in their group
-  if (tid < a.n_obj * ngrp) {
-    const int g = tid % ngrp;
-    a.ticket[(tid / ngrp * kAccGroups + g) * kTicketStride] = (acc_wgs - g + ngrp - 1) / ngrp * kAccWaves;
-  }
-  __syncthreads();
-  for (int n = tid; n < a.n; n += kSetupThreads) {
-    const int r = (int)(a.x[2 * (long long)n] - (double)a.lo0);
-    const int c = (int)(a.x[2 * (long long)n + 1] - (double)a.lo1);
-    a.rc[2 * n] = r;
-    a.rc[2 * n + 1] = c;
-    col[n] = c;
-    atomicAdd(cnt + c, 1);
-  }
-  __syncthreads();
-  // the non-empty columns as (column, count) in 15 + 13 bits (C <= 2^15, n <= 4096); any order
-  for (int c = tid; c < a.C; c += kSetupThreads) {
-    const int h = cnt[c];
-    if (h > 0) clist[atomicAdd(misc, 1)] = c | (h << 15);
-  }
-  __syncthreads();
-  setup_scan(cnt, a.C + 1, part, a.cstart);
-  // stable placement: the rank of n among the earlier points of its column
-  for (int n = tid; n < a.n; n += kSetupThreads) {
-    const int c = col[n];
-    int rank = 0;
-    for (int m = 0; m < n; ++m) rank += col[m] == c ? 1 : 0;
-    a.order[cnt[c] + rank] = n;
-  }
-  // pairs per tau (the K padding of the contraction and the scan's last entry stay 0): a wave per
-  // column c, the lanes over c' >= c, 8 reads in flight ahead of their atomics.  (Measured at C3,
-  // ~400 non-empty columns: 25 us, the longest part of this kernel; a gather form without atomics
-  // -- a thread per tau over the sorted non-empty columns -- took 32 us unrolled by 8, 48 us plain)
-  const int ncol = misc[0];
-  for (int i = wave; i < ncol; i += kSetupWaves) {
-    const int ei = clist[i], ci = ei & 32767, hi = ei >> 15;
-    for (int j0 = i + lane; j0 < ncol; j0 += 64 * 8) {
-      int ej[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) ej[u] = j0 + 64 * u < ncol ? clist[j0 + 64 * u] : -1;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (ej[u] >= 0)
-          atomicAdd(tcnt + ci + (ej[u] & 32767), j0 + 64 * u == i ? hi * (hi + 1) / 2 : hi * (ej[u] >> 15));
-    }
-  }
-  __syncthreads();
-  {
-    int mx = 0;
-    for (int t = tid; t < a.LT; t += kSetupThreads) mx = tcnt[t] > mx ? tcnt[t] : mx;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-      const int o = __shfl_xor(mx, d, 64);
-      mx = o > mx ? o : mx;
-    }
-    if (lane == 0) atomicMax(misc + 1, mx);
-  }
-  __syncthreads();
-  // (no more items than waves: every wave takes the one item of its index, and their order is moot)
-  const int npass = !dyn ? 0 : misc[1] < 256 ? 1 : misc[1] < 65536 ? 2 : 3;
-  const int chunk = ((a.LT + kSetupWaves - 1) / kSetupWaves + 63) / 64 * 64;
-  const int e_lo = wave * chunk, e_hi = e_lo + chunk < a.LT ? e_lo + chunk : a.LT;
-  unsigned short *pa = perm, *pb = perm + a.LT;
-  for (int pass = 0; pass < npass; ++pass) {
-    for (int t = tid; t < 256 * kSetupWaves; t += kSetupThreads) wcnt[t] = 0;
-    __syncthreads();
-    for (int e = e_lo + lane; e < e_hi; e += 64) {
-      const int tau = pass == 0 ? e : pa[e];
-      const int d = 255 - ((tcnt[tau] >> (8 * pass)) & 255);
-      atomicAdd(wcnt + d * kSetupWaves + wave, 1);
-    }
-    __syncthreads();
-    setup_scan(wcnt, 256 * kSetupWaves, part, nullptr);
-    for (int e0 = e_lo; e0 < e_hi; e0 += 64) {
-      const int e = e0 + lane;
-      const bool valid = e < e_hi;
-      const int tau = !valid ? 0 : pass == 0 ? e : pa[e];
-      const int d = 255 - ((tcnt[tau] >> (8 * pass)) & 255);
-      unsigned long long m = __ballot(valid);               // the valid lanes of this lane's digit
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1;
-        const unsigned long long bal = __ballot(valid && bit);
-        m &= bit ? bal : ~bal;
-      }
-      const unsigned long long below = m & ((1ull << lane) - 1ull);
-      int* slot = wcnt + d * kSetupWaves + wave;              // this wave's next place for the digit
-      const int base = valid ? *slot : 0;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      if (valid) {
-        pb[base + __popcll(below)] = (unsigned short)tau;
-        if (below == 0ull) *slot = base + __popcll(m);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    __syncthreads();
-    unsigned short* t = pa;
-    pa = pb;
-    pb = t;
-  }
-  for (int t = tid; t < a.LT; t += kSetupThreads) a.torder[t] = npass ? pa[t] : t;
-  setup_scan(tcnt, a.LT + 1, part, a.pstart);
-}
-
 // ---------------------------------------------------------------------------------------
 // Pair list.  blockIdx.x < tau_blocks: the lists of kListWaves values of tau; the blocks after
 // them: Tm for every objective.
@@ -240,7 +83,10 @@ __global__ __launch_bounds__(kSetupThreads) void conv_setup_kernel(const ConvArg
 // order -- lane l owns a contiguous range of n, counts its pairs (the partner bucket is column
 // tau - c_n, the m >= n of it), a wave scan gives every n its place in the list -- written to the
 // workspace at pstart[tau] as the table base of r_n + r_m (once) and w_nm (per objective; the
-// integer part of the list is the same for every objective).  Only the pairs with |w_nm| >=
+// integer part of the list is the same for every objective).  pstart[tau], the pairs of every
+// smaller tau, is the wave's own sum over the column buckets (no counts of other tau, no scan; the
+// layout is that of an exclusive scan of the counts), written for the accumulate kernel.
+// Only the pairs with |w_nm| >=
 // kPairDrop pv for some objective are written, closed up in unchanged order (a ballot per 64 pairs
 // and the wave's running count); pkept[tau] is their number (0 for an empty tau and for the padding
 // tau up to LT).  The criterion reads the call's inputs alone, so every shard keeps the same pairs.
@@ -248,7 +94,29 @@ __global__ __launch_bounds__(kSetupThreads) void conv_setup_kernel(const ConvArg
 //   E(2i - sigma) = tabE[par * 2R + i + (s >> 1)],  s = 2R - 2 - sigma,  par = s & 1.
 // LDS: cstart[C + 1] | order[n] | rc[2n]
 // ---------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvArgs a, int tau_blocks) {
+// The end of a tau's list wave: pkept; a tau that kept nothing (empty, padding, or every pair dropped)
+// gets its T rows written here as +0.0 and is no item of the accumulate kernel; with tickets (dyn) a
+// tau that kept k pairs is appended to the list of its class and shard.
+__device__ __forceinline__ void conv_list_done(const ConvArgs& a, int tau, int kept, int lane, int dyn) {
+  if (kept == 0) {
+    for (int o = 0; o < a.n_obj; ++o) {
+      double* row = a.T + ((size_t)o * a.LT + tau) * a.ldr;
+      for (int i = lane; i < a.ldr; i += 64) row[i] = 0.0;
+    }
+  }
+  if (lane == 0) {
+    a.pkept[tau] = kept;
+    if (dyn && kept > 0) {
+      const int e = 31 - __clz(kept);
+      const int cls = 2 * e + (e > 0 ? (kept >> (e - 1)) & 1 : 0);
+      const int sh = tau & (kShards - 1);
+      const int slot = atomicAdd(a.ccount + cls * kCountStride + sh, 1);
+      a.clist[(size_t)(cls * kShards + sh) * (a.LT / kShards) + slot] = tau;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvArgs a, int tau_blocks, int dyn) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= tau_blocks) {
@@ -283,10 +151,27 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
   int* nm = rc + 2 * a.n + wave * kListChunk;          // the wave's slice: (n, m) in 16 + 16 bits
   const int tau = blockIdx.x * kListWaves + wave;
   if (tau >= a.LT) return;
-  const int p0 = __builtin_amdgcn_readfirstlane(a.pstart[tau]);
-  const int total = __builtin_amdgcn_readfirstlane(a.pstart[tau + 1]) - p0;
+  // the pairs n <= m with c_n + c_m < t, from the column buckets alone: with h[c] the points of column
+  // c and cum(x) = cstart[clamp(x, 0, C)], the ordered pairs are sum_c h[c] cum(t - c); the n = m among
+  // them (2 c_n < t) were counted once, every other pair twice.  At most n^2 + n <= 2^24 + 2^12.
+  int s0 = 0, s1 = 0;                                 // t = tau and t = tau + 1
+  for (int c = lane; c < a.C; c += 64) {
+    const int h = cstart[c + 1] - cstart[c];
+    const int x0 = tau - c, x1 = x0 + 1;
+    s0 += h * cstart[x0 < 0 ? 0 : x0 > a.C ? a.C : x0];
+    s1 += h * cstart[x1 < 0 ? 0 : x1 > a.C ? a.C : x1];
+  }
+#pragma unroll
+  for (int d = 32; d > 0; d >>= 1) {
+    s0 += __shfl_xor(s0, d, 64);
+    s1 += __shfl_xor(s1, d, 64);
+  }
+  const int h0 = (tau + 1) >> 1, h1 = (tau + 2) >> 1;
+  const int p0 = __builtin_amdgcn_readfirstlane((s0 + cstart[h0 > a.C ? a.C : h0]) >> 1);
+  const int total = __builtin_amdgcn_readfirstlane((s1 + cstart[h1 > a.C ? a.C : h1]) >> 1) - p0;
+  if (lane == 0) a.pstart[tau] = p0;
   if (total == 0) {                                   // (the padding tau >= 2C - 1 among them)
-    if (lane == 0) a.pkept[tau] = 0;
+    conv_list_done(a, tau, 0, lane, dyn);
     return;
   }
   const int R2 = 2 * a.R;
@@ -372,17 +257,21 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
   }
-  if (lane == 0) a.pkept[tau] = kept;
+  conv_list_done(a, tau, kept, lane, dyn);
 }
 
 // ---------------------------------------------------------------------------------------
-// Accumulate.  blockIdx.y = objective.  A work item is (tau, block of kAccRows rows); item t of an
-// objective is row block t % nrb of tau torder[t / nrb], so the longest lists start first.
+// Accumulate.  blockIdx.y = objective.  A work item is (tau, block of kAccRows rows) of a tau that
+// kept pairs; item t of an objective is row block t % nrb of the tau at position t / nrb of the class
+// lists, taken from the class of the longest lists down (a class spans a factor below 2 in length:
+// longest first up to that; the exact sort gave the same makespan in the greedy model of DESIGN.md §9).
 // Persistent waves take the items through the objective's ticket (one lane's integer atomicAdd);
 // no wave waits for another.  A wave runs down its tau's list -- w and the table base are
 // wave-uniform loads -- and accumulates w E(2i - sigma) in list order, kAccRB rows per lane, with a
-// compensated sum.  A T entry is produced by one wave in list order: the ticket order is in no value.
-// LDS: tabE[2][2R]
+// compensated sum.  A T entry is produced by one wave in list order: neither the ticket order nor the
+// order inside a class list is in any value.  Without tickets (no more items than waves) item t's tau
+// is t / nrb, and a tau that kept nothing is skipped.
+// LDS: tabE[2][2R] | cst[kClassLists + 1] | part[waves]
 // ---------------------------------------------------------------------------------------
 // FULL: every row of the block is a row of the shard (the table offsets of the lane's rows are
 // immediates); else rows past the shard's (the padding to ldr) read a valid table entry and are
@@ -458,7 +347,8 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
                                                                   const int* __restrict__ pair_sl,
                                                                   const int* __restrict__ pstart,
                                                                   const int* __restrict__ pkept,
-                                                                  const int* __restrict__ torder,
+                                                                  const int* __restrict__ ccount,
+                                                                  const int* __restrict__ clist,
                                                                   int* __restrict__ ticket, double* __restrict__ T,
                                                                   int nrb, int ngrp, int dyn) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
@@ -467,29 +357,72 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
   const double nhl = a.nhl[o];
   const int R2 = 2 * a.R;
   double* tabE = sd;
+  int* cst = (int*)(tabE + 2 * R2);                   // [kClassLists + 1] first position of each class list
+  int* part = cst + (kClassLists + 1);                // [kAccWaves]
   for (int t = tid; t < 2 * R2; t += 64 * kAccWaves) {
     const int par = t >= R2 ? 1 : 0, h = t - par * R2;
     const double m = (double)(2 * h + par - (R2 - 2));
     tabE[t] = exp(0.5 * nhl * (m * m));
   }
+  if (dyn) {
+    // the class lists one after the other, the longest class first (the shards of a class in turn):
+    // list j is class kClasses - 1 - j / kShards, shard j % kShards; an exclusive scan of their lengths,
+    // two lists per thread
+    int c[2], sum = 0;
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = 2 * tid + u;
+      c[u] = j < kClassLists ? ccount[(kClasses - 1 - j / kShards) * kCountStride + j % kShards] : 0;
+      sum += c[u];
+    }
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int v = __shfl_up(incl, d, 64);
+      if (lane >= d) incl += v;
+    }
+    if (lane == 63) part[tid >> 6] = incl;
+    __syncthreads();
+    int run = incl - sum;
+    for (int w = 0; w < (tid >> 6); ++w) run += part[w];
+#pragma unroll
+    for (int u = 0; u < 2; ++u) {
+      const int j = 2 * tid + u;
+      if (j < kClassLists) cst[j] = run;
+      run += c[u];
+      if (j == kClassLists - 1) cst[kClassLists] = run;
+    }
+  }
   __syncthreads();
-  const int n_items = a.LT * nrb;
+  // (with tickets: the tau that kept pairs; a tau that kept nothing has its rows from the list kernel)
+  const int n_items = (dyn ? cst[kClassLists] : a.LT) * nrb;
   const double* wo = pair_w + (size_t)o * a.n_pairs;
   // group g = blockIdx.x % ngrp owns the items g, g + ngrp, ... and a ticket of its own; a wave's
-  // first item is its own index in the group (the setup kernel starts the tickets behind them)
+  // first item is its own index in the group (the setup block starts the tickets behind them)
   const int g = blockIdx.x % ngrp;
   int* tk = ticket + (o * kAccGroups + g) * kTicketStride;
   for (int k = (blockIdx.x / ngrp) * kAccWaves + (tid >> 6);;) {
     const int t = k * ngrp + g;
     if (t >= n_items) break;
-    // the next ticket is taken before this item's work, which hides its round trip (the items at
-    // the end of the order, where a reserved item could be waited for, are the empty tau)
+    // the next ticket is taken before this item's work, which hides its round trip
     int nx = 0;
     if (dyn && lane == 0) nx = atomicAdd(tk, 1);
     const int oi = t / nrb, rb = t - oi * nrb;
-    const int tau = __builtin_amdgcn_readfirstlane(torder[oi]);
+    int tau = oi;
+    if (dyn) {
+      // the list that holds position oi: the first whose end is past it.  Lane l looks at the last
+      // of its kClassLists / 64 lists, then the lanes at the lists of the lane found
+      constexpr int per = kClassLists / 64;
+      const unsigned long long b1 = __ballot(cst[per * lane + per] > oi);
+      const int l1 = __builtin_ctzll(b1);
+      const unsigned long long b2 = __ballot(cst[per * l1 + (lane < per ? lane : per - 1) + 1] > oi);
+      const int j = per * l1 + __builtin_ctzll(b2);
+      const int* list = clist + (size_t)((kClasses - 1 - j / kShards) * kShards + j % kShards) * (a.LT / kShards);
+      tau = __builtin_amdgcn_readfirstlane(list[oi - cst[j]]);
+    }
     const int p0 = __builtin_amdgcn_readfirstlane(pstart[tau]);
     const int cnt = __builtin_amdgcn_readfirstlane(pkept[tau]);        // the pairs that the list kept
+    if (!dyn && cnt == 0) break;           // its rows are the list kernel's
     const int ib = rb * kAccRows;
     double* Trow = T + ((size_t)o * a.LT + tau) * a.ldr;
     if (ib + kAccRows <= a.nrows) conv_acc_item<true>(tabE, wo + p0, pair_sl + p0, cnt, ib, lane, a.nrows, a.ldr, Trow);
@@ -826,46 +759,49 @@ static hipError_t conv_lds_attr(K k, size_t lds) {
   return hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
 }
 
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, int cus, hipStream_t st) {
+// The accumulate kernel's persistent waves: up to 4 workgroups (4 waves per SIMD) per CU as the
+// table's LDS allows, shared evenly by the objectives; no more waves than the bound LT nrb on its
+// items (their number is the device's: the tau that kept pairs).
+ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus) {
+  ConvSched sc;
+  sc.nrb = (ldr + kAccRows - 1) / kAccRows;
+  const long long items = (long long)LT * sc.nrb;
+  const size_t tab = (size_t)4 * R * sizeof(double);
+  const int per_cu = (int)(kConvLdsBytes / tab < 4 ? kConvLdsBytes / tab : 4);
+  long long wgs = (long long)(cus > 0 ? cus : 256) * per_cu / n_obj;
+  if (wgs > (items + kAccWaves - 1) / kAccWaves) wgs = (items + kAccWaves - 1) / kAccWaves;
+  if (wgs < 1) wgs = 1;
+  sc.wgs = (int)wgs;
+  sc.ngrp = (int)(wgs < kAccGroups ? wgs : kAccGroups);
+  // tickets only when some wave can have a second item: not when the groups are of equal size and
+  // hold no more items than waves (a wave's first item is its index in its group)
+  sc.dyn = (items <= wgs * kAccWaves && wgs % sc.ngrp == 0) ? 0 : 1;
+  return sc;
+}
+
+hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st) {
   // The kernels' own LDS.  The plan's bounds dominate them: conv_lds_contract is about 48 C bytes, so
   // C <= ~3400 (LT <= 6800), conv_lds_pair is 32 R + 24 KiB + ..., so R <= ~4300, and n <= 4096.  At
-  // those extremes setup needs 4 (3 C + 2 n) + 4 LT + 16.5 KiB = ~117 KiB, the list kernel
-  // 4 (C + 3 n) + 8 KiB = ~71 KiB, the accumulate kernel 32 R = ~135 KiB: all below 160 KiB, so the
-  // check below cannot fire for a planned call (it guards a future change of the plan's bounds)
-  const size_t l0 = ((size_t)ca.C + 1 + ca.n + kSetupWaves + (ca.LT + 1) + (ca.n < ca.C ? ca.n : ca.C) + 2 +
-                     256 * kSetupWaves) * sizeof(int) + (size_t)2 * ca.LT * sizeof(unsigned short);
+  // those extremes the list kernel needs 4 (C + 3 n) + 8 KiB = ~71 KiB, the accumulate kernel
+  // 32 R + 2 KiB = ~137 KiB: all below 160 KiB, so the check below cannot fire for a planned call (it
+  // guards a future change of the plan's bounds)
   const size_t l1 = ((size_t)(ca.C + 1) + 3 * (size_t)ca.n + kListWaves * kListChunk) * sizeof(int);
-  const size_t la = (size_t)4 * ca.R * sizeof(double);
+  const size_t la = (size_t)4 * ca.R * sizeof(double) + (size_t)(kClassLists + 1 + kAccWaves + 1) / 2 * 2 * sizeof(int);
   const size_t l2 = conv_lds_contract(ca.n, ca.C);
-  if (l0 > kConvLdsBytes || l1 > kConvLdsBytes || la > kConvLdsBytes || ca.LT > 65536) return hipErrorInvalidValue;
+  if (l1 > kConvLdsBytes || la > kConvLdsBytes) return hipErrorInvalidValue;
   hipError_t e;
-  if ((e = conv_lds_attr(conv_setup_kernel, l0)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_list_kernel, l1)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_acc_kernel, la)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_contract_kernel, l2)) != hipSuccess) return e;
-  // the accumulate kernel's persistent waves: up to 4 workgroups (4 waves per SIMD) per CU as the
-  // table's LDS allows, shared evenly by the objectives; no more waves than items
-  const int nrb = (ca.ldr + kAccRows - 1) / kAccRows;
-  const long long items = (long long)ca.LT * nrb;
-  const int per_cu = (int)(kConvLdsBytes / la < 4 ? kConvLdsBytes / la : 4);
-  long long wgs = (long long)(cus > 0 ? cus : 256) * per_cu / ca.n_obj;
-  if (wgs > (items + kAccWaves - 1) / kAccWaves) wgs = (items + kAccWaves - 1) / kAccWaves;
-  if (wgs < 1) wgs = 1;
-  const int ngrp = (int)(wgs < kAccGroups ? wgs : kAccGroups);
-  // tickets only when some wave has a second item: not when the groups are of equal size and hold
-  // no more items than waves (a wave's first item is its index in its group)
-  const int dyn = (items <= wgs * kAccWaves && wgs % ngrp == 0) ? 0 : 1;
-  hipLaunchKernelGGL(conv_setup_kernel, dim3(1), dim3(kSetupThreads), l0, st, ca, (int)wgs, ngrp, dyn);
-  if ((e = hipGetLastError()) != hipSuccess) return e;
   const int tau_blocks = (ca.LT + kListWaves - 1) / kListWaves;    // the padding tau too: their pkept
   const long long tm_elems = (long long)ca.NP * ca.ldr;
   const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 512 ? (tm_elems + 1023) / 1024 : 512);
-  hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks);
+  hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks,
+                     sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)wgs, ca.n_obj), dim3(64 * kAccWaves), la, st, ca,
+  hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)sc.wgs, ca.n_obj), dim3(64 * kAccWaves), la, st, ca,
                      (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.pkept,
-                     (const int*)ca.torder,
-                     ca.ticket, ca.T, nrb, ngrp, dyn);
+                     (const int*)ca.ccount, (const int*)ca.clist, ca.ticket, ca.T, sc.nrb, sc.ngrp, sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(conv_contract_kernel, dim3(grid), dim3(256), l2, st, ca);
   return hipGetLastError();

@@ -311,7 +311,7 @@ __device__ void pack32_range(long long t0, long long stride, f4* __restrict__ ou
 
 
 // ---------------------------------------------------------------------------------------
-// Per-call preparation, ONE launch (blocks by role; the two single-block roles, serial chains of
+// Per-call preparation, ONE launch (blocks by role; the single-block roles, serial chains of
 // dependent memory round trips, come first so that they are dispatched before the bulk):
 //   block 0                        training rows: xpad (original; padded rows 1e200 so their
 //                                  K* is exactly 0) and xc = x - x_0 (centred); the
@@ -319,6 +319,8 @@ __device__ void pack32_range(long long t0, long long stride, f4* __restrict__ ou
 //                                  coordinate an integer on the grid's last axis); the
 //                                  evaluated points padded to [n_excl][DIM];
 //   block 1                        the hash set of the exclusion rows (zeroed, then filled);
+//   block 2 (grid convolution      its setup (conv_setup_block, bo_predict_impl.h): integer coordinates,
+//   planned; else absent)          column buckets, the accumulate kernel's tickets and class counters;
 //   [2, 2 + alpha_blocks)          alpha[o][f] = sum_e K^-1[o][f][e] (y[e][o] - pm[o])
 //                                  (numba_kernels.py:477-483), one wave per row, e ascending
 //                                  per lane then a shuffle tree;
@@ -356,6 +358,8 @@ struct PrepArgs {
   unsigned int hslots;
   int n_hash;                            // rows to insert (0: no table)
   int hash_lds;                          // 1: built in the launch's dynamic LDS, then stored
+  int conv_setup;                        // 1: block 2 is the grid-convolution path's setup (conv_setup_block)
+  bo::ConvSetupArgs cs;
 };
 
 __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
@@ -438,7 +442,12 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
     }
     return;
   }
-  b -= 2;
+  if (p.conv_setup && b == 2) {
+    extern __shared__ __attribute__((aligned(16))) int conv_lds[];
+    bo::conv_setup_block<256>(p.cs, conv_lds);
+    return;
+  }
+  b -= 2 + p.conv_setup;
   const int lane = tid & 63, wave = tid >> 6;
   if (b < p.alpha_blocks) {
     const long long row_id = (long long)b * 4 + wave;
@@ -508,7 +517,7 @@ int num_cus() {
 //   k-block of the contraction), BO_PREDICT_NO_GRID_CONV and BO_GRID_CONV=0 (environment, read here:
 //   fixed when a graph is captured) never plan it.
 constexpr double kConvMargin = 1.15;
-constexpr int kConvMaxN = 4096;          // conv_setup_kernel ranks a point against all earlier ones
+constexpr int kConvMaxN = 4096;          // (n, m) of a pair in 16 + 16 bits, pair counts below 2^24
 
 void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
   if (kmem || !pl->cm || d->cand_kind != BO_CAND_GRID || d->dim != 2 || d->n_cand <= 0) return;
@@ -549,10 +558,12 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
   const long long wgs = (n_wt + 3) / 4;
   pl->conv_grid = (int)(wgs < pl->grid ? wgs : pl->grid);
   pl->off_conv_ints = align256(pl->total);
-  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT + 1] | torder[LT] | pkept[LT] | tickets (a line each)
+  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT] | pkept[LT] | clist[kConvClasses][LT] | tickets (a line
+  // each) | class counters (a line per class)
   pl->off_conv_Tm = pl->off_conv_ints +
-                    align256((size_t)(C + 1 + 3 * n + 3 * pl->conv_LT + 1 + 32) * sizeof(int) +
-                             (size_t)BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride * sizeof(int));
+                    align256((size_t)(C + 1 + 3 * n + (2 + bo::kConvClasses) * pl->conv_LT + 32) * sizeof(int) +
+                             (size_t)BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride * sizeof(int) +
+                             (size_t)bo::kConvClasses * bo::kConvCountStride * sizeof(int));
   pl->off_conv_T = pl->off_conv_Tm + align256((size_t)d->n_obj * pl->conv_NP * pl->conv_ldr * sizeof(double));
   pl->off_conv_sl = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
   // the pair list: every pair n <= m has one tau, so its length is known here
@@ -831,6 +842,72 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   fa.rw_stride = pl.rw_stride;
   fa.off_exp = pl.off_exp;
   fa.conv_flag = pl.conv ? conv_flag : nullptr;
+  // the grid-convolution path's arguments and the schedule of its accumulate kernel: the prep launch's
+  // setup block writes the buckets, the tickets and the counters that the kernels behind it read
+  bo::ConvArgs ca;
+  bo::ConvSched csched;
+  memset(&csched, 0, sizeof(csched));
+  memset(&ca, 0, sizeof(ca));
+  if (pl.conv) {
+    ca.n_obj = d->n_obj;
+    ca.n = (int)d->n_train;
+    ca.n_pad = pl.n_pad;
+    ca.R = (int)d->grid_shape[0];
+    ca.C = (int)d->grid_shape[1];
+    ca.lo0 = d->grid_lo[0];
+    ca.lo1 = d->grid_lo[1];
+    ca.cand_offset = d->cand_offset;
+    ca.n_cand = d->n_cand;
+    ca.ld_out = fa.ld_out;
+    ca.row_lo = pl.conv_row_lo;
+    ca.nrows = pl.conv_nrows;
+    ca.ldr = pl.conv_ldr;
+    ca.LT = pl.conv_LT;
+    ca.NP = pl.conv_NP;
+    ca.Cpad = pl.conv_Cpad;
+    ca.flag = conv_flag;
+    ca.x = d->x_train;
+    ca.kinv = d->kinv;
+    ca.ld_k = d->ld_k;
+    ca.alpha = alpha;
+    for (int o = 0; o < d->n_obj; ++o) {
+      ca.pm[o] = fa.pm[o];
+      ca.pv[o] = fa.pv[o];
+      ca.nhl[o] = fa.nhl[o];
+      ca.beta[o] = fa.beta[o];
+      ca.inv_rsq_pv[o] = fa.inv_rsq_pv[o];
+      ca.inv_pv[o] = fa.inv_pv[o];
+    }
+    ca.min_var = fa.min_var;
+    ca.cstart = (int*)(ws + pl.off_conv_ints);
+    ca.order = ca.cstart + (ca.C + 1);
+    ca.rc = ca.order + ca.n;
+    ca.pstart = ca.rc + 2 * ca.n;
+    ca.pkept = ca.pstart + ca.LT;
+    ca.clist = ca.pkept + ca.LT;
+    ca.ticket = (int*)(((uintptr_t)(ca.clist + (size_t)bo::kConvClasses * ca.LT) + 127) & ~(uintptr_t)127);
+    ca.ccount = ca.ticket + BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride;
+    ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
+    ca.n_pairs = pl.conv_pairs;
+    ca.pair_sl = (int*)(ws + pl.off_conv_sl);
+    ca.pair_w = (double*)(ws + pl.off_conv_w);
+    ca.Tm = (double*)(ws + pl.off_conv_Tm);
+    ca.T = (double*)(ws + pl.off_conv_T);
+    ca.mu = d->mu;
+    ca.var = d->var;
+    ca.std_mu = d->std_mu;
+    ca.std_var = d->std_var;
+    ca.ucb = d->ucb;
+    ca.acq = d->acq;
+    ca.topq = d->topq;
+    ca.partial = partial;
+    ca.n_lists = pl.grid * pl.waves;
+    ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
+    ca.hkeys = fa.hkeys;
+    ca.hidx = fa.hidx;
+    ca.hmask = fa.hmask;
+    csched = bo::conv_acc_schedule(ca.R, ca.LT, ca.ldr, ca.n_obj, num_cus());
+  }
   {
     PrepArgs pa;
     memset(&pa, 0, sizeof(pa));
@@ -874,9 +951,33 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     pa.hslots = pl.hash_slots;
     pa.n_hash = (kmem || d->topq == 0) ? 0 : pl.n_excl;
     pa.hash_lds = pa.n_hash > 0 && pl.hash_slots <= 2048 ? 1 : 0;     // <= 24 KiB of LDS
-    const size_t prep_lds = pa.hash_lds ? (size_t)pl.hash_slots * 12 : 0;
-    hipLaunchKernelGGL(predict_prep_kernel, dim3((unsigned)(2 + pa.alpha_blocks + pa.pack_blocks)), dim3(256),
-                       prep_lds, s, pa);
+    size_t prep_lds = pa.hash_lds ? (size_t)pl.hash_slots * 12 : 0;
+    if (pl.conv) {
+      pa.conv_setup = 1;
+      pa.cs.x = d->x_train;
+      pa.cs.n = ca.n;
+      pa.cs.n_obj = ca.n_obj;
+      pa.cs.R = ca.R;
+      pa.cs.C = ca.C;
+      pa.cs.lo0 = ca.lo0;
+      pa.cs.lo1 = ca.lo1;
+      pa.cs.rc = ca.rc;
+      pa.cs.cstart = ca.cstart;
+      pa.cs.order = ca.order;
+      pa.cs.ticket = ca.ticket;
+      pa.cs.ccount = ca.ccount;
+      pa.cs.acc_wgs = csched.wgs;
+      pa.cs.ngrp = csched.ngrp;
+      // (the plan keeps conv_lds_setup within the 160 KiB)
+      const size_t setup_lds = bo::conv_lds_setup(ca.n, ca.C);
+      if (setup_lds > prep_lds) prep_lds = setup_lds;
+    }
+    if (prep_lds > 64 * 1024)
+      BO_CHECK_HIP(hipFuncSetAttribute((const void*)predict_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                       (int)prep_lds));
+    hipLaunchKernelGGL(predict_prep_kernel,
+                       dim3((unsigned)(2 + pa.conv_setup + pa.alpha_blocks + pa.pack_blocks)), dim3(256), prep_lds, s,
+                       pa);
     BO_CHECK_HIP(hipGetLastError());
   }
   if (d->n_cand == 0) {
@@ -891,65 +992,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   if (pl.conv) {
     // the grid-convolution kernels and the chunk-major kernel are both enqueued; the device flag
     // lets one of them run (no host synchronisation: the call stays capturable)
-    bo::ConvArgs ca;
-    memset(&ca, 0, sizeof(ca));
-    ca.n_obj = d->n_obj;
-    ca.n = (int)d->n_train;
-    ca.n_pad = pl.n_pad;
-    ca.R = (int)d->grid_shape[0];
-    ca.C = (int)d->grid_shape[1];
-    ca.lo0 = d->grid_lo[0];
-    ca.lo1 = d->grid_lo[1];
-    ca.cand_offset = d->cand_offset;
-    ca.n_cand = d->n_cand;
-    ca.ld_out = fa.ld_out;
-    ca.row_lo = pl.conv_row_lo;
-    ca.nrows = pl.conv_nrows;
-    ca.ldr = pl.conv_ldr;
-    ca.LT = pl.conv_LT;
-    ca.NP = pl.conv_NP;
-    ca.Cpad = pl.conv_Cpad;
-    ca.flag = conv_flag;
-    ca.x = d->x_train;
-    ca.kinv = d->kinv;
-    ca.ld_k = d->ld_k;
-    ca.alpha = alpha;
-    for (int o = 0; o < d->n_obj; ++o) {
-      ca.pm[o] = fa.pm[o];
-      ca.pv[o] = fa.pv[o];
-      ca.nhl[o] = fa.nhl[o];
-      ca.beta[o] = fa.beta[o];
-      ca.inv_rsq_pv[o] = fa.inv_rsq_pv[o];
-      ca.inv_pv[o] = fa.inv_pv[o];
-    }
-    ca.min_var = fa.min_var;
-    ca.cstart = (int*)(ws + pl.off_conv_ints);
-    ca.order = ca.cstart + (ca.C + 1);
-    ca.rc = ca.order + ca.n;
-    ca.pstart = ca.rc + 2 * ca.n;
-    ca.torder = ca.pstart + (ca.LT + 1);
-    ca.pkept = ca.torder + ca.LT;
-    ca.ticket = (int*)(((uintptr_t)(ca.pkept + ca.LT) + 127) & ~(uintptr_t)127);
-    ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
-    ca.n_pairs = pl.conv_pairs;
-    ca.pair_sl = (int*)(ws + pl.off_conv_sl);
-    ca.pair_w = (double*)(ws + pl.off_conv_w);
-    ca.Tm = (double*)(ws + pl.off_conv_Tm);
-    ca.T = (double*)(ws + pl.off_conv_T);
-    ca.mu = d->mu;
-    ca.var = d->var;
-    ca.std_mu = d->std_mu;
-    ca.std_var = d->std_var;
-    ca.ucb = d->ucb;
-    ca.acq = d->acq;
-    ca.topq = d->topq;
-    ca.partial = partial;
-    ca.n_lists = pl.grid * pl.waves;
-    ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
-    ca.hkeys = fa.hkeys;
-    ca.hidx = fa.hidx;
-    ca.hmask = fa.hmask;
-    if (bo::launch_gridconv(ca, pl.conv_grid, num_cus(), s) != hipSuccess) return BO_ERR_HIP;
+    if (bo::launch_gridconv(ca, pl.conv_grid, csched, s) != hipSuccess) return BO_ERR_HIP;
   }
   if (kmem) e = launch_kmem(pl, fa, s);
   else if (pl.fp32) switch (pl.dim_pad) {

@@ -93,10 +93,14 @@ struct ConvArgs {
   int* cstart;                           // [C + 1] first slot of each column's bucket
   int* order;                            // [n] training points sorted by column (stable)
   int* rc;                               // [n][2] integer coordinates (row, column)
-  int* pstart;                           // [LT + 1] first slot of each tau's pairs in the pair list
+  int* pstart;                           // [LT] first slot of each tau's pairs in the pair list (the list kernel's
+                                         // tau-wave computes it from cstart and writes it)
   int* pkept;                            // [LT] pairs of each tau that the list kept (|w| >= 2^-100 pv for some
                                          // objective), compacted at pstart[tau]
-  int* torder;                           // [LT] the tau by descending pair count, ties by ascending tau
+  int* ccount;                           // [kConvClasses] lines of kConvShards counters (stride kConvCountStride):
+                                         // the tau that kept pairs, by class of pkept and shard tau % kConvShards
+  int* clist;                            // [kConvClasses][kConvShards][LT / kConvShards] those tau, in the order
+                                         // their list waves finished (an order of work, in no value)
   int* ticket;                           // [BO_MAX_OBJ][kConvTicketGroups] (stride kConvTicketStride): the next
                                          // work item of each group of the accumulate kernel's workgroups
   int n_pairs;                           // n (n + 1) / 2: pairs n <= m, every one in exactly one tau
@@ -117,14 +121,137 @@ struct ConvArgs {
 
 constexpr int kConvTicketGroups = 32;    // tickets per objective
 constexpr int kConvTicketStride = 32;    // ints between two tickets (one 128-byte line each)
+// the accumulate kernel's work order: the tau in classes of their kept pair count k, class =
+// 2 floor(log2 k) + (the bit below the leading one): half-octaves, at most 48 for k < 2^24
+constexpr int kConvClasses = 64;
+#ifndef BO_CONV_SHARDS
+#define BO_CONV_SHARDS 8                 // BO_BUILD_VARIANT=DEF_CONV_SHARDS=1: the A/B of DESIGN.md §9
+#endif
+constexpr int kConvShards = BO_CONV_SHARDS;   // counters per class (tau % kConvShards): a power of two <= 16
+constexpr int kConvCountStride = 32;     // ints between two classes' counters (one 128-byte line each)
+constexpr int kConvAccWaves = 4;         // waves per workgroup of the accumulate kernel
 
-// LDS bounds that the plan tests (the pair stage's kernels launch with less than conv_lds_pair);
-// launch of the whole sequence (setup, pair list, accumulate, contraction): `grid` workgroups of
-// the contraction, `cus` compute units for the persistent accumulate kernel
+// The accumulate kernel's persistent grid (conv_acc_schedule): decided on the host before the prep
+// launch, whose setup block starts the tickets for it.
+struct ConvSched {
+  int nrb;                               // row blocks per tau
+  int wgs, ngrp;                         // workgroups per objective; groups of them, a ticket each
+  int dyn;                               // 1: some wave takes a second item (tickets and class lists in use)
+};
+
+// Arguments of the setup block of the prep launch (conv_setup_block).
+struct ConvSetupArgs {
+  const double* x;                       // [n][2] training points
+  int n, n_obj, R, C;
+  long long lo0, lo1;
+  int *rc, *cstart, *order, *ticket, *ccount;   // as in ConvArgs
+  int acc_wgs, ngrp;                     // ConvSched
+};
+
+// exclusive scan of v[0 .. len) in place over a workgroup of THREADS, also written to out (if given);
+// part[THREADS / 64].  Contiguous segments per thread, a wave scan of their sums, the waves' totals.
+template <int THREADS>
+__device__ __forceinline__ void conv_scan(int* v, int len, int* part, int* out) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int seg = (len + THREADS - 1) / THREADS;
+  const int c_lo = tid * seg < len ? tid * seg : len, c_hi = c_lo + seg < len ? c_lo + seg : len;
+  int sum = 0;
+  for (int c = c_lo; c < c_hi; ++c) sum += v[c];
+  int incl = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) part[wave] = incl;
+  __syncthreads();
+  int run = incl - sum;
+  for (int w = 0; w < wave; ++w) run += part[w];
+  for (int c = c_lo; c < c_hi; ++c) {
+    const int t = v[c];
+    v[c] = run;
+    if (out) out[c] = run;
+    run += t;
+  }
+  __syncthreads();
+}
+
+// Setup of the grid-convolution path, one workgroup of THREADS (a role block of the prep launch):
+// rc[n] = integer (row, column) of training point n; cstart / order = the points bucketed by column,
+// ascending n inside a bucket (the pair list's order, and with it T's bits, follow it); the start
+// values of the accumulate kernel's tickets and the zeroed class counters.
+// The block runs beside the one that checks that every training point is a grid point, so it cannot
+// know the answer: a coordinate is clamped into the grid (a NaN to 0), which changes nothing for a
+// grid point and keeps every index in range otherwise -- then the flag stops the kernels that would
+// read what is written here.
+// Stable placement: wave 0 takes the points 64 at a time in ascending n; the lanes of equal column
+// (found by a ballot per bit of the column) take consecutive places from their column's running
+// place in LDS.  N / 64 steps of two LDS round trips, where ranking a point against every earlier one
+// took N^2 / THREADS comparisons per thread.
+// LDS (ints): cnt[C + 1] | col[n] | part[THREADS / 64]
+template <int THREADS>
+__device__ __forceinline__ void conv_setup_block(const ConvSetupArgs& a, int* lds) {
+  int* cnt = lds;
+  int* col = cnt + (a.C + 1);
+  int* part = col + a.n;
+  const int tid = threadIdx.x, lane = tid & 63;
+  for (int c = tid; c <= a.C; c += THREADS) cnt[c] = 0;
+  // the first items of the accumulate kernel's waves are their own indices in their group
+  for (int t = tid; t < a.n_obj * a.ngrp; t += THREADS) {
+    const int g = t % a.ngrp;
+    a.ticket[(t / a.ngrp * kConvTicketGroups + g) * kConvTicketStride] =
+        (a.acc_wgs - g + a.ngrp - 1) / a.ngrp * kConvAccWaves;
+  }
+  for (int t = tid; t < kConvClasses * kConvShards; t += THREADS)
+    a.ccount[t / kConvShards * kConvCountStride + t % kConvShards] = 0;
+  __syncthreads();
+  for (int n = tid; n < a.n; n += THREADS) {
+    // (fmax / fmin return the other operand for a NaN)
+    const int r = (int)fmin(fmax(a.x[2 * (long long)n] - (double)a.lo0, 0.0), (double)(a.R - 1));
+    const int c = (int)fmin(fmax(a.x[2 * (long long)n + 1] - (double)a.lo1, 0.0), (double)(a.C - 1));
+    a.rc[2 * n] = r;
+    a.rc[2 * n + 1] = c;
+    col[n] = c;
+    atomicAdd(cnt + c, 1);
+  }
+  __syncthreads();
+  conv_scan<THREADS>(cnt, a.C + 1, part, a.cstart);
+  if (tid >= 64) return;
+  const int bits = a.C > 1 ? 32 - __clz(a.C - 1) : 0;
+  for (int n0 = 0; n0 < a.n; n0 += 64) {
+    const int n = n0 + lane;
+    const bool valid = n < a.n;
+    const int c = valid ? col[n] : 0;
+    unsigned long long m = __ballot(valid);                 // the valid lanes of this lane's column
+    for (int b = 0; b < bits; ++b) {
+      const bool bit = (c >> b) & 1;
+      const unsigned long long bal = __ballot(valid && bit);
+      m &= bit ? bal : ~bal;
+    }
+    const unsigned long long below = m & ((1ull << lane) - 1ull);
+    const int base = valid ? cnt[c] : 0;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (valid) {
+      a.order[base + __popcll(below)] = n;
+      if (below == 0ull) cnt[c] = base + __popcll(m);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  }
+}
+
+// LDS bounds that the plan tests (the pair stage's kernels launch with less than conv_lds_pair;
+// conv_lds_setup covers conv_setup_block and is what the prep launch asks for it);
+// the accumulate kernel's schedule on `cus` compute units; launch of the sequence behind the prep
+// launch (pair list, accumulate, contraction): `grid` workgroups of the contraction
 size_t conv_lds_setup(int n, int C);
 size_t conv_lds_pair(int n, int R, int C);
 size_t conv_lds_contract(int n, int C);
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, int cus, hipStream_t st);
+ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus);
+hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st);
 
 // Host-side plan of one bo_predict_acquire call (bo_predict.hip: make_plan).
 struct Plan {
