@@ -15,20 +15,10 @@
 // the same N^2 products as k' K^-1 k (update_variance, numba_kernels.py:491-535), grouped so that
 // a candidate costs 2 (2C - 1) + 2 N matrix-core flops per objective instead of N^2.
 //
-// The setup is a role block of the prep launch (conv_setup_block, bo_predict_impl.h): integer
-// coordinates; training points bucketed by column (stable counting sort); the tickets' start values,
-// the class counters zeroed.  Then three launches, each returning at once unless the device flag
-// (predict_prep_kernel) says that every training point is a grid point:
-//   conv_list_kernel      the pair list (one wave per tau): its offset from the column buckets in
-//                         closed form, table base once, w_nm per objective, without the pairs that
-//                         are negligible for every objective (kPairDrop); the tau appended to the
-//                         list of its class of kept pairs, or its T rows zeroed when it kept none;
-//                         and Tm[s][i] = pv alpha_n H(i - r_n), n = order[s];
-//   conv_acc_kernel       T: persistent waves take (tau, row block) items from the class lists,
-//                         the class of the longest lists first;
-//   conv_contract_kernel  the two GEMMs on v_mfma_f64_16x16x4_f64 over the k-blocks inside a tile's
-//                         band (kTabFlush), the epilogue of cm_predict_kernel, per-wave top-q lists
-//                         in the TopEntry partial layout.
+// The setup is a role block of the prep launch (conv_setup_block, bo_predict_impl.h); then three launches, each
+// returning at once unless the device flag (predict_prep_kernel) says that every training point is a grid
+// point: conv_list_kernel (the pair list and Tm), conv_acc_kernel (T) and conv_contract_kernel (the two GEMMs,
+// the epilogue and the selection), each described where it stands.
 // No floating-point atomics (the tickets are integers and order work, not sums); every sum runs
 // in an order fixed by the inputs alone, and the K order of an output element does not depend on
 // its tile, so shards reproduce the single call.
@@ -37,14 +27,10 @@
 
 namespace {
 
-using bo::ConvArgs;
+using namespace bo;   // ConvArgs, ConvSched and the kConv* constants they share with the setup block
 
-// the LDS layout of the removed one-kernel pair stage, kept for conv_lds_pair alone (the plan's gate)
-constexpr int kPairChunk = 256;
-constexpr int kTauPerWg = 8;
 constexpr int kListWaves = 4;            // waves per workgroup of the list kernel, one tau each
 constexpr int kListChunk = 512;          // pairs of one tau staged in LDS at a time (per wave)
-constexpr int kAccWaves = bo::kConvAccWaves;   // waves per workgroup of the accumulate kernel
 // rows per lane of a work item.  BO_BUILD_VARIANT=DEF_ACC_RB=16 builds the other candidate (A/B in
 // DESIGN.md §9)
 #ifndef BO_ACC_RB
@@ -53,19 +39,10 @@ constexpr int kAccWaves = bo::kConvAccWaves;   // waves per workgroup of the acc
 constexpr int kAccRB = BO_ACC_RB;
 constexpr int kAccRows = 64 * kAccRB;    // rows of a work item (tau, row block)
 constexpr int kAccUnroll = 4;            // list entries loaded ahead of their terms
-// tickets per objective, each on a cache line of its own.  One ticket per objective made the kernel
-// as long as its atomics: ~25 ns each on one address from 8 XCDs, 6,000 of them at C3 (160 us)
-constexpr int kAccGroups = bo::kConvTicketGroups;
-constexpr int kTicketStride = bo::kConvTicketStride;
-// the work order of the accumulate kernel: the tau that kept pairs, appended by their list waves to
-// the list of their class (half-octaves of the kept count) and shard (tau % kShards: 400 to 630 tau
-// share a class at C3, and their atomics on one address would queue)
-constexpr int kClasses = bo::kConvClasses;
-constexpr int kShards = bo::kConvShards;
-constexpr int kCountStride = bo::kConvCountStride;
-constexpr int kClassLists = kClasses * kShards;
-static_assert(kClassLists % 64 == 0 && kClassLists <= 2 * 64 * kAccWaves && (kShards & (kShards - 1)) == 0 &&
-              kShards <= 16 && kShards <= kCountStride, "conv_acc_kernel's scan and lookup of the class lists");
+constexpr int kClassLists = kConvClasses * kConvShards;   // the class lists of the accumulate kernel's work order
+static_assert(kClassLists % 64 == 0 && kClassLists <= 2 * 64 * kConvAccWaves &&
+              (kConvShards & (kConvShards - 1)) == 0 && kConvShards <= 16 && kConvShards <= kConvCountStride,
+              "conv_acc_kernel's scan and lookup of the class lists");
 constexpr int kConvPF = 3;               // A-operand prefetch depth of the contraction (k-blocks)
 constexpr size_t kConvLdsBytes = 160 * 1024;
 // a pair whose |w_nm| is below kPairDrop pv for every objective is left out of the list: at most
@@ -74,6 +51,29 @@ constexpr double kPairDrop = 0x1p-100;
 // entries of the contraction's tables below kTabFlush are stored as +0.0: the k-blocks whose
 // entries are all zero for a tile add nothing to it and are not run
 constexpr double kTabFlush = 0x1p-128;
+
+// The dynamic LDS of each kernel, described once: the kernel carves its pointers from the layout and
+// launch_gridconv takes the launch's bytes from the same object.
+struct ListLds {         // ints: cstart[C + 1] | order[n] | rc[2n] | nm[kListWaves][kListChunk]
+  int order, rc, nm;
+  size_t bytes;
+  __host__ __device__ ListLds(int n, int C)
+      : order(C + 1), rc(order + n), nm(rc + 2 * n), bytes((size_t)(nm + kListWaves * kListChunk) * sizeof(int)) {}
+};
+struct AccLds {          // doubles: tabE[2][2R]; then ints, to a whole double: cst[kClassLists + 1] | part[waves]
+  int ints, part;        // `ints` in doubles, `part` in ints from there
+  size_t bytes;
+  __host__ __device__ explicit AccLds(int R)
+      : ints(4 * R), part(kClassLists + 1),
+        bytes((size_t)ints * sizeof(double) + (size_t)(part + kConvAccWaves + 1) / 2 * 2 * sizeof(int)) {}
+};
+struct ContractLds {     // doubles: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] (ints, one double); then ints: cn[NP]
+  int HB, tabH, hband, cn;
+  size_t bytes;
+  __host__ __device__ ContractLds(int C, int Cpad, int LT, int NP)
+      : HB(Cpad + LT / 2), tabH(2 * HB), hband(tabH + Cpad + C - 1), cn(hband + 1),
+        bytes((size_t)cn * sizeof(double) + (size_t)NP * sizeof(int)) {}
+};
 
 // ---------------------------------------------------------------------------------------
 // Pair list.  blockIdx.x < tau_blocks: the lists of kListWaves values of tau; the blocks after
@@ -92,7 +92,6 @@ constexpr double kTabFlush = 0x1p-128;
 // tau up to LT).  The criterion reads the call's inputs alone, so every shard keeps the same pairs.
 // E table of the accumulate kernel, split by parity so that consecutive rows read consecutive doubles:
 //   E(2i - sigma) = tabE[par * 2R + i + (s >> 1)],  s = 2R - 2 - sigma,  par = s & 1.
-// LDS: cstart[C + 1] | order[n] | rc[2n]
 // ---------------------------------------------------------------------------------------
 // The end of a tau's list wave: pkept; a tau that kept nothing (empty, padding, or every pair dropped)
 // gets its T rows written here as +0.0 and is no item of the accumulate kernel; with tickets (dyn) a
@@ -109,9 +108,9 @@ __device__ __forceinline__ void conv_list_done(const ConvArgs& a, int tau, int k
     if (dyn && kept > 0) {
       const int e = 31 - __clz(kept);
       const int cls = 2 * e + (e > 0 ? (kept >> (e - 1)) & 1 : 0);
-      const int sh = tau & (kShards - 1);
-      const int slot = atomicAdd(a.ccount + cls * kCountStride + sh, 1);
-      a.clist[(size_t)(cls * kShards + sh) * (a.LT / kShards) + slot] = tau;
+      const int sh = tau & (kConvShards - 1);
+      const int slot = atomicAdd(a.ccount + cls * kConvCountStride + sh, 1);
+      a.clist[(size_t)(cls * kConvShards + sh) * (a.LT / kConvShards) + slot] = tau;
     }
   }
 }
@@ -140,15 +139,16 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
     return;
   }
   extern __shared__ __attribute__((aligned(16))) int si[];
+  const ListLds L(a.n, a.C);
   int* cstart = si;
-  int* order = cstart + (a.C + 1);
-  int* rc = order + a.n;
+  int* order = si + L.order;
+  int* rc = si + L.rc;
   for (int t = tid; t <= a.C; t += 64 * kListWaves) cstart[t] = a.cstart[t];
   for (int t = tid; t < a.n; t += 64 * kListWaves) order[t] = a.order[t];
   for (int t = tid; t < 2 * a.n; t += 64 * kListWaves) rc[t] = a.rc[t];
   __syncthreads();
   const int lane = tid & 63, wave = tid >> 6;
-  int* nm = rc + 2 * a.n + wave * kListChunk;          // the wave's slice: (n, m) in 16 + 16 bits
+  int* nm = si + L.nm + wave * kListChunk;             // the wave's slice: (n, m) in 16 + 16 bits
   const int tau = blockIdx.x * kListWaves + wave;
   if (tau >= a.LT) return;
   // the pairs n <= m with c_n + c_m < t, from the column buckets alone: with h[c] the points of column
@@ -271,7 +271,6 @@ __global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvAr
 // compensated sum.  A T entry is produced by one wave in list order: neither the ticket order nor the
 // order inside a class list is in any value.  Without tickets (no more items than waves) item t's tau
 // is t / nrb, and a tau that kept nothing is skipped.
-// LDS: tabE[2][2R] | cst[kClassLists + 1] | part[waves]
 // ---------------------------------------------------------------------------------------
 // FULL: every row of the block is a row of the shard (the table offsets of the lane's rows are
 // immediates); else rows past the shard's (the padding to ldr) read a valid table entry and are
@@ -343,36 +342,34 @@ __device__ __forceinline__ void conv_acc_item(const double* tabE, const double* 
   }
 }
 
-__global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs a, const double* __restrict__ pair_w,
-                                                                  const int* __restrict__ pair_sl,
-                                                                  const int* __restrict__ pstart,
-                                                                  const int* __restrict__ pkept,
-                                                                  const int* __restrict__ ccount,
-                                                                  const int* __restrict__ clist,
-                                                                  int* __restrict__ ticket, double* __restrict__ T,
-                                                                  int nrb, int ngrp, int dyn) {
+// (seven of ConvArgs' pointers again as __restrict__ parameters: the compiler's alias information)
+__global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
+    const ConvArgs a, const double* __restrict__ pair_w, const int* __restrict__ pair_sl,
+    const int* __restrict__ pstart, const int* __restrict__ pkept, const int* __restrict__ ccount,
+    const int* __restrict__ clist, int* __restrict__ ticket, double* __restrict__ T, int nrb, int ngrp, int dyn) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   extern __shared__ __attribute__((aligned(16))) double sd[];
   const int tid = threadIdx.x, lane = tid & 63, o = blockIdx.y;
   const double nhl = a.nhl[o];
   const int R2 = 2 * a.R;
+  const AccLds L(a.R);
   double* tabE = sd;
-  int* cst = (int*)(tabE + 2 * R2);                   // [kClassLists + 1] first position of each class list
-  int* part = cst + (kClassLists + 1);                // [kAccWaves]
-  for (int t = tid; t < 2 * R2; t += 64 * kAccWaves) {
+  int* cst = (int*)(sd + L.ints);                     // first position of each class list
+  int* part = cst + L.part;
+  for (int t = tid; t < 2 * R2; t += 64 * kConvAccWaves) {
     const int par = t >= R2 ? 1 : 0, h = t - par * R2;
     const double m = (double)(2 * h + par - (R2 - 2));
     tabE[t] = exp(0.5 * nhl * (m * m));
   }
   if (dyn) {
     // the class lists one after the other, the longest class first (the shards of a class in turn):
-    // list j is class kClasses - 1 - j / kShards, shard j % kShards; an exclusive scan of their lengths,
-    // two lists per thread
+    // list j is class kConvClasses - 1 - j / kConvShards, shard j % kConvShards; an exclusive scan of their
+    // lengths, two lists per thread
     int c[2], sum = 0;
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int j = 2 * tid + u;
-      c[u] = j < kClassLists ? ccount[(kClasses - 1 - j / kShards) * kCountStride + j % kShards] : 0;
+      c[u] = j < kClassLists ? ccount[(kConvClasses - 1 - j / kConvShards) * kConvCountStride + j % kConvShards] : 0;
       sum += c[u];
     }
     int incl = sum;
@@ -400,8 +397,8 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
   // group g = blockIdx.x % ngrp owns the items g, g + ngrp, ... and a ticket of its own; a wave's
   // first item is its own index in the group (the setup block starts the tickets behind them)
   const int g = blockIdx.x % ngrp;
-  int* tk = ticket + (o * kAccGroups + g) * kTicketStride;
-  for (int k = (blockIdx.x / ngrp) * kAccWaves + (tid >> 6);;) {
+  int* tk = ticket + (o * kConvTicketGroups + g) * kConvTicketStride;
+  for (int k = (blockIdx.x / ngrp) * kConvAccWaves + (tid >> 6);;) {
     const int t = k * ngrp + g;
     if (t >= n_items) break;
     // the next ticket is taken before this item's work, which hides its round trip
@@ -417,7 +414,8 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
       const int l1 = __builtin_ctzll(b1);
       const unsigned long long b2 = __ballot(cst[per * l1 + (lane < per ? lane : per - 1) + 1] > oi);
       const int j = per * l1 + __builtin_ctzll(b2);
-      const int* list = clist + (size_t)((kClasses - 1 - j / kShards) * kShards + j % kShards) * (a.LT / kShards);
+      const int cls = kConvClasses - 1 - j / kConvShards;
+      const int* list = clist + (size_t)(cls * kConvShards + j % kConvShards) * (a.LT / kConvShards);
       tau = __builtin_amdgcn_readfirstlane(list[oi - cst[j]]);
     }
     const int p0 = __builtin_amdgcn_readfirstlane(pstart[tau]);
@@ -443,7 +441,7 @@ __global__ __launch_bounds__(64 * kAccWaves) void conv_acc_kernel(const ConvArgs
 //                (split by parity: consecutive columns read consecutive doubles);
 //      mean      H(j - c_n)  = tabH[j - c_n + C - 1]; the rows of Tm and cn[] are the training points
 //                in column-bucketed order (`order`), so the points near a tile are consecutive rows.
-// LDS: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] | cn[NP]; rebuilt per objective.
+// The tables tabB, tabH and hband (ContractLds) are rebuilt when the length scale changes.
 // Bands: table entries below kTabFlush are stored as +0.0, and hband holds the largest |t| of an entry
 // that the same comparison kept (hq for E, hm for H).  A tile of columns j0 .. j0 + 63 runs
 //   variance  the k-blocks that hold a tau of [2 j0 - hq, 2 (j0 + 63) + hq],
@@ -493,12 +491,12 @@ __device__ __forceinline__ void conv_gemm(const double* __restrict__ X, int ldr,
 __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   extern __shared__ __attribute__((aligned(16))) double sd[];
-  const int HB = a.Cpad + a.LT / 2;
+  const ContractLds L(a.C, a.Cpad, a.LT, a.NP);
   double* tabB = sd;
-  double* tabH = tabB + 2 * HB;
+  double* tabH = sd + L.tabH;
   // (the last entry of tabH's region is read by no tile: j - c_n + C - 1 <= Cpad + C - 2)
-  int* hband = (int*)(tabH + (a.Cpad + a.C - 1));                // [2] the bands of tabB and tabH: hq, hm
-  int* cn = (int*)(tabH + (a.Cpad + a.C));
+  int* hband = (int*)(sd + L.hband);                             // the bands of tabB and tabH: hq, hm
+  int* cn = (int*)(sd + L.cn);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int g = lane >> 4, jl = lane & 15;
   const int cb_n = a.Cpad / 64;                                  // wave tiles along a grid row
@@ -526,8 +524,8 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
         // entries below kTabFlush become +0.0 (a NaN entry compares false and stays); the band is
         // the largest |t| that the same comparison kept
         int mq = 0;
-        for (int t = tid; t < 2 * HB; t += 256) {
-          const int par = t >= HB ? 1 : 0, h = t - par * HB;
+        for (int t = tid; t < 2 * L.HB; t += 256) {
+          const int par = t >= L.HB ? 1 : 0, h = t - par * L.HB;
           const int mi = 2 * h + par - (a.LT - 1);
           const double m = (double)mi;
           const double v = exp(0.5 * nhl * (m * m));
@@ -592,7 +590,7 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
       const double* pe0 = tabB + (a.LT / 2 - 1 - 8 * kq_lo - 2 * g) + j0 + jl;
       conv_gemm(Tq, a.ldr, kq_hi - kq_lo, g, aq, [&](int kb, double (&bv)[4][4]) {
         const double* pe = pe0 - 8 * kb;                         // even u
-        const double* po = pe + HB;                              // odd u
+        const double* po = pe + L.HB;                              // odd u
 #pragma unroll
         for (int nb = 0; nb < 4; ++nb) {
           bv[0][nb] = po[16 * nb];
@@ -740,17 +738,14 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
 
 namespace bo {
 
-size_t conv_lds_setup(int n, int C) { return ((size_t)(C + 1) + n + 256) * sizeof(int); }
-
-size_t conv_lds_pair(int n, int R, int C) {
-  return ((size_t)4 * R + kTauPerWg * kPairChunk) * sizeof(double) +
-         ((size_t)(C + 1) + 3 * (size_t)n + kTauPerWg * kPairChunk) * sizeof(int);
-}
-
-size_t conv_lds_contract(int n, int C) {
-  const size_t Cpad = ((size_t)C + 63) / 64 * 64, LT = ((size_t)2 * C - 1 + 15) / 16 * 16;
-  const size_t NP = ((size_t)n + 15) / 16 * 16;
-  return (2 * (Cpad + LT / 2) + Cpad + C) * sizeof(double) + NP * sizeof(int);
+// The plan's admission bound on (n, R, C), frozen: it decides which calls take this path (conv_planned of
+// tests/gridconv_model.py mirrors it) and is the LDS of no kernel -- the tables of R, C and n plus 2048 doubles
+// and 2048 ints.  The real layouts of the setup block, the list and the accumulate kernel each hold a part of its
+// terms and are smaller for every (n, R, C); the contraction's tables are tested by themselves.
+bool conv_lds_admits(int n, int R, int C, int Cpad, int LT, int NP) {
+  const size_t bound = ((size_t)4 * R + 2048) * sizeof(double) + ((size_t)(C + 1) + 3 * (size_t)n + 2048) * sizeof(int);
+  assert(ConvSetupLds(n, C, 256).bytes <= bound && ListLds(n, C).bytes <= bound && AccLds(R).bytes <= bound);
+  return bound <= kConvLdsBytes && ContractLds(C, Cpad, LT, NP).bytes <= kConvLdsBytes;
 }
 
 template <class K>
@@ -769,26 +764,20 @@ ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus) {
   const size_t tab = (size_t)4 * R * sizeof(double);
   const int per_cu = (int)(kConvLdsBytes / tab < 4 ? kConvLdsBytes / tab : 4);
   long long wgs = (long long)(cus > 0 ? cus : 256) * per_cu / n_obj;
-  if (wgs > (items + kAccWaves - 1) / kAccWaves) wgs = (items + kAccWaves - 1) / kAccWaves;
+  if (wgs > (items + kConvAccWaves - 1) / kConvAccWaves) wgs = (items + kConvAccWaves - 1) / kConvAccWaves;
   if (wgs < 1) wgs = 1;
   sc.wgs = (int)wgs;
-  sc.ngrp = (int)(wgs < kAccGroups ? wgs : kAccGroups);
+  sc.ngrp = (int)(wgs < kConvTicketGroups ? wgs : kConvTicketGroups);
   // tickets only when some wave can have a second item: not when the groups are of equal size and
   // hold no more items than waves (a wave's first item is its index in its group)
-  sc.dyn = (items <= wgs * kAccWaves && wgs % sc.ngrp == 0) ? 0 : 1;
+  sc.dyn = (items <= wgs * kConvAccWaves && wgs % sc.ngrp == 0) ? 0 : 1;
   return sc;
 }
 
 hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st) {
-  // The kernels' own LDS.  The plan's bounds dominate them: conv_lds_contract is about 48 C bytes, so
-  // C <= ~3400 (LT <= 6800), conv_lds_pair is 32 R + 24 KiB + ..., so R <= ~4300, and n <= 4096.  At
-  // those extremes the list kernel needs 4 (C + 3 n) + 8 KiB = ~71 KiB, the accumulate kernel
-  // 32 R + 2 KiB = ~137 KiB: all below 160 KiB, so the check below cannot fire for a planned call (it
-  // guards a future change of the plan's bounds)
-  const size_t l1 = ((size_t)(ca.C + 1) + 3 * (size_t)ca.n + kListWaves * kListChunk) * sizeof(int);
-  const size_t la = (size_t)4 * ca.R * sizeof(double) + (size_t)(kClassLists + 1 + kAccWaves + 1) / 2 * 2 * sizeof(int);
-  const size_t l2 = conv_lds_contract(ca.n, ca.C);
-  if (l1 > kConvLdsBytes || la > kConvLdsBytes) return hipErrorInvalidValue;
+  const size_t l1 = ListLds(ca.n, ca.C).bytes, la = AccLds(ca.R).bytes;
+  const size_t l2 = ContractLds(ca.C, ca.Cpad, ca.LT, ca.NP).bytes;
+  if (l1 > kConvLdsBytes || la > kConvLdsBytes) return hipErrorInvalidValue;   // (conv_lds_admits keeps them below)
   hipError_t e;
   if ((e = conv_lds_attr(conv_list_kernel, l1)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_acc_kernel, la)) != hipSuccess) return e;
@@ -799,7 +788,7 @@ hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hi
   hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks,
                      sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)sc.wgs, ca.n_obj), dim3(64 * kAccWaves), la, st, ca,
+  hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)sc.wgs, ca.n_obj), dim3(64 * kConvAccWaves), la, st, ca,
                      (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.pkept,
                      (const int*)ca.ccount, (const int*)ca.clist, ca.ticket, ca.T, sc.nrb, sc.ngrp, sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;

@@ -321,7 +321,7 @@ __device__ void pack32_range(long long t0, long long stride, f4* __restrict__ ou
 //   block 1                        the hash set of the exclusion rows (zeroed, then filled);
 //   block 2 (grid convolution      its setup (conv_setup_block, bo_predict_impl.h): integer coordinates,
 //   planned; else absent)          column buckets, the accumulate kernel's tickets and class counters;
-//   [2, 2 + alpha_blocks)          alpha[o][f] = sum_e K^-1[o][f][e] (y[e][o] - pm[o])
+//   [2 or 3, .. + alpha_blocks)    alpha[o][f] = sum_e K^-1[o][f][e] (y[e][o] - pm[o])
 //                                  (numba_kernels.py:477-483), one wave per row, e ascending
 //                                  per lane then a shuffle tree;
 //   [.., + pack_blocks)            W packed into the kernel's MFMA stream (pack_cm_range /
@@ -345,9 +345,6 @@ struct PrepArgs {
   int* sep_flag;                         // NULL: no separable grid check
   long long sep_lo;
   int sep_S;
-  int* conv_flag;                        // NULL: no grid-convolution check (bo_gridconv.hip)
-  long long conv_lo[2];
-  int conv_ext[2];
   double* excl;
   const double* excl_in;
   int n_excl;
@@ -358,8 +355,10 @@ struct PrepArgs {
   unsigned int hslots;
   int n_hash;                            // rows to insert (0: no table)
   int hash_lds;                          // 1: built in the launch's dynamic LDS, then stored
-  int conv_setup;                        // 1: block 2 is the grid-convolution path's setup (conv_setup_block)
-  bo::ConvSetupArgs cs;
+  // the grid-convolution path's arguments and schedule (bo_gridconv.hip).  conv.flag NULL: not planned; else block 0
+  // writes the flag and block 2 is the path's setup (conv_setup_block)
+  bo::ConvArgs conv;
+  bo::ConvSched sched;
 };
 
 __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
@@ -381,11 +380,11 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
         sep_bad |= !ok;
       }
       // grid-convolution precondition: the training point is a point of the 2-D grid
-      if (f < p.n && p.conv_flag) {
+      if (f < p.n && p.conv.flag) {
         for (int k = 0; k < 2; ++k) {
           const double v = p.x[(long long)f * p.dim + k];
-          const bool ok = v == __builtin_rint(v) && v >= (double)p.conv_lo[k] &&
-                          v <= (double)(p.conv_lo[k] + p.conv_ext[k] - 1);
+          const long long lo = k ? p.conv.lo1 : p.conv.lo0, hi = lo + (k ? p.conv.C : p.conv.R) - 1;
+          const bool ok = v == __builtin_rint(v) && v >= (double)lo && v <= (double)hi;
           conv_bad |= !ok;
         }
       }
@@ -393,7 +392,7 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
     const int any_bad = __syncthreads_or(sep_bad);
     if (tid == 0 && p.sep_flag) *p.sep_flag = any_bad ? 1 : 0;
     const int any_conv_bad = __syncthreads_or(conv_bad);
-    if (tid == 0 && p.conv_flag) *p.conv_flag = any_conv_bad ? 1 : 0;
+    if (tid == 0 && p.conv.flag) *p.conv.flag = any_conv_bad ? 1 : 0;
     for (int t = tid; t < p.n_excl * p.DIM; t += 256) {
       const int r = t / p.DIM, k = t - r * p.DIM;
       p.excl[t] = k < p.dim ? p.excl_in[(long long)r * p.dim + k] : 0.0;
@@ -442,12 +441,12 @@ __global__ __launch_bounds__(256) void predict_prep_kernel(const PrepArgs p) {
     }
     return;
   }
-  if (p.conv_setup && b == 2) {
+  if (p.conv.flag && b == 2) {
     extern __shared__ __attribute__((aligned(16))) int conv_lds[];
-    bo::conv_setup_block<256>(p.cs, conv_lds);
+    bo::conv_setup_block<256>(p.conv, p.sched, conv_lds);
     return;
   }
-  b -= 2 + p.conv_setup;
+  b -= p.conv.flag ? 3 : 2;
   const int lane = tid & 63, wave = tid >> 6;
   if (b < p.alpha_blocks) {
     const long long row_id = (long long)b * 4 + wave;
@@ -502,17 +501,12 @@ int num_cus() {
 // The grid-convolution path (bo_gridconv.hip): planned for a 2-D integer grid in the
 // default (upper, separable, f64) mode when its kernels' tables fit the LDS and the cost gate
 // passes; whether the training points are grid points is known only on the device (conv flag).
-//   gate: margin x (modelled time of the new sequence) < modelled time of the chunk-major kernel.
-//   A ratio of matrix-core flops does not predict the crossover (measured, DESIGN.md §9: at a
-//   64 x 64 grid the flop ratio is 5-8 and the new path 3-14x SLOWER): the new path has fixed
-//   launches, its pair stage is one serial wave per tau, and small grids leave most SIMDs idle in
-//   both paths.  The model, in microseconds on MI355X (256 CUs), constants fitted to that table:
-//     new  = 60 + 2.2 x (pairs per tau) x (1024-row blocks) x (rounds of 4096 tau-waves)
-//               + (rounds of 1024 wave tiles) x 2 x 16 x 64 x (LT + NP) x n_obj / 48.8e3
-//            (the contraction at its measured 50 TF: 48.8e3 flops per us and wave slot)
-//     old  = 25 + (rounds of 256 tiles of 64 candidates) x 64 x (F / 273e3 + 0.038),
-//            F = n_obj 1024 nch (nch + 1) MFMA flops per candidate at the measured 70 TF.
-//   Both sides reproduce the 15 measured points within 20 %; the margin covers that.
+//   gate: margin x (modelled time of the new sequence) < modelled time of the chunk-major kernel, in
+//   microseconds on MI355X (256 CUs).  A ratio of matrix-core flops does not predict the crossover (at a
+//   64 x 64 grid it is 5-8 and the path was measured 3-14x SLOWER): the path has fixed launches, its pair stage
+//   is VALU work (a list wave per tau, then the accumulate kernel's items), and small grids leave most SIMDs
+//   idle in both paths.  DESIGN.md §9.5 has the model behind the constants below and the table they were
+//   fitted to; both sides reproduce its 15 points within 20 %, which the margin covers.
 //   BO_PREDICT_GRID_CONV skips the gate (so does BO_PREDICT_GRID_CONV_FULL, which also runs every
 //   k-block of the contraction), BO_PREDICT_NO_GRID_CONV and BO_GRID_CONV=0 (environment, read here:
 //   fixed when a graph is captured) never plan it.
@@ -527,49 +521,34 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
   const long long R = d->grid_shape[0], C = d->grid_shape[1], n = d->n_train;
   if (R < 1 || C < 1 || R > (1 << 15) || C > (1 << 15) || n > kConvMaxN) return;
   if (d->cand_offset < 0 || d->cand_offset + d->n_cand > R * C) return;
-  if (bo::conv_lds_setup((int)n, (int)C) > kLdsBytes || bo::conv_lds_pair((int)n, (int)R, (int)C) > kLdsBytes ||
-      bo::conv_lds_contract((int)n, (int)C) > kLdsBytes)
-    return;
-  const long long row_lo = d->cand_offset / C, row_hi = (d->cand_offset + d->n_cand - 1) / C;
-  const long long nrows = row_hi - row_lo + 1;
+  bo::ConvPlan cp = {};
+  cp.row_lo = (int)(d->cand_offset / C);
+  cp.nrows = (int)((d->cand_offset + d->n_cand - 1) / C) - cp.row_lo + 1;
+  cp.ldr = (cp.nrows + 15) / 16 * 16;
+  cp.Cpad = (int)((C + 63) / 64 * 64);
+  cp.LT = (int)((2 * C - 1 + 15) / 16 * 16);
+  cp.NP = (int)((n + 15) / 16 * 16);
+  if (!bo::conv_lds_admits((int)n, (int)R, (int)C, cp.Cpad, cp.LT, cp.NP)) return;
+  const long long wave_tiles = (long long)(cp.ldr / 16) * (cp.Cpad / 64);
   if (!(d->mode & (BO_PREDICT_GRID_CONV | BO_PREDICT_GRID_CONV_FULL))) {
     const double nch = pl->n_pad / 32;
     const double F = (double)d->n_obj * 1024.0 * nch * (nch + 1);
     const double old_rounds = (double)(((d->n_cand + 63) / 64 + 255) / 256);
     const double old_us = 25.0 + old_rounds * 64.0 * (F / 273.0e3 + 0.038);
-    const long long ldr = (nrows + 15) / 16 * 16, Cpad = (C + 63) / 64 * 64;
-    const long long LT = (2 * C - 1 + 15) / 16 * 16, NP = (n + 15) / 16 * 16;
     const double pairs_per_tau = 0.5 * (double)n * (double)(n + 1) / (double)(2 * C - 1);
-    const double pair_us = 2.2 * pairs_per_tau * (double)((ldr + 1023) / 1024) *
+    const double pair_us = 2.2 * pairs_per_tau * (double)((cp.ldr + 1023) / 1024) *
                            (double)((d->n_obj * (2 * C - 1) + 4095) / 4096);
-    const double tile_rounds = (double)(((ldr / 16) * (Cpad / 64) + 1023) / 1024);
-    const double contract_us = tile_rounds * 2048.0 * (double)(LT + NP) * (double)d->n_obj / 48.8e3;
+    const double tile_rounds = (double)((wave_tiles + 1023) / 1024);
+    const double contract_us = tile_rounds * 2048.0 * (double)(cp.LT + cp.NP) * (double)d->n_obj / 48.8e3;
     const double conv_us = 60.0 + pair_us + contract_us;
     if (!(kConvMargin * conv_us < old_us)) return;
   }
-  pl->conv = true;
-  pl->conv_row_lo = (int)row_lo;
-  pl->conv_nrows = (int)nrows;
-  pl->conv_ldr = (int)((nrows + 15) / 16 * 16);
-  pl->conv_LT = (int)((2 * C - 1 + 15) / 16 * 16);
-  pl->conv_NP = (int)((n + 15) / 16 * 16);
-  pl->conv_Cpad = (int)((C + 63) / 64 * 64);
-  const long long n_wt = (long long)(pl->conv_ldr / 16) * (pl->conv_Cpad / 64);
-  const long long wgs = (n_wt + 3) / 4;
-  pl->conv_grid = (int)(wgs < pl->grid ? wgs : pl->grid);
-  pl->off_conv_ints = align256(pl->total);
-  // ints: cstart[C + 1] | order[n] | rc[2n] | pstart[LT] | pkept[LT] | clist[kConvClasses][LT] | tickets (a line
-  // each) | class counters (a line per class)
-  pl->off_conv_Tm = pl->off_conv_ints +
-                    align256((size_t)(C + 1 + 3 * n + (2 + bo::kConvClasses) * pl->conv_LT + 32) * sizeof(int) +
-                             (size_t)BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride * sizeof(int) +
-                             (size_t)bo::kConvClasses * bo::kConvCountStride * sizeof(int));
-  pl->off_conv_T = pl->off_conv_Tm + align256((size_t)d->n_obj * pl->conv_NP * pl->conv_ldr * sizeof(double));
-  pl->off_conv_sl = pl->off_conv_T + align256((size_t)d->n_obj * pl->conv_LT * pl->conv_ldr * sizeof(double));
-  // the pair list: every pair n <= m has one tau, so its length is known here
-  pl->conv_pairs = (int)(n * (n + 1) / 2);
-  pl->off_conv_w = pl->off_conv_sl + align256((size_t)pl->conv_pairs * sizeof(int));
-  pl->total = pl->off_conv_w + align256((size_t)d->n_obj * pl->conv_pairs * sizeof(double));
+  cp.planned = true;
+  const long long wgs = (wave_tiles + 3) / 4;
+  cp.grid = (int)(wgs < pl->grid ? wgs : pl->grid);
+  cp.ws = bo::conv_layout(n, d->n_obj, C, cp.LT, cp.NP, cp.ldr, align256(pl->total));
+  pl->total = cp.ws.end;
+  pl->conv = cp;
 }
 
 // Kernel choice and workspace layout of one call.
@@ -738,31 +717,29 @@ size_t bo_predict_workspace_size(const bo_predict_desc* d) {
   return pl.total;
 }
 
-static int predict_impl(const bo_predict_desc* d, const double* kstar, long long ks_rows,
-                        void* workspace, size_t ws_bytes, void* stream) {
-  const bool kmem = kstar != nullptr;
-  Plan pl;
-  int st = make_plan(d, &pl, true, kmem);
-  if (st != BO_OK) return st;
+// The checks of a call's arguments against its plan, in the order in which their errors are reported.
+static int validate_call(const bo_predict_desc* d, const Plan& pl, bool kmem, const void* workspace, size_t ws_bytes) {
   if (!workspace || ws_bytes < pl.total) return BO_ERR_WORKSPACE;
   if ((!kmem && !d->x_train) || !d->y_train || !d->kinv || d->ld_k < d->n_train ||
       d->ld_y < d->n_obj)
     return BO_ERR_ARG;
   if (d->cand_kind != BO_CAND_GRID && d->n_cand > 0 && !d->cand) return BO_ERR_ARG;
   if (d->topq > 0 && (!d->top_val || !d->top_idx)) return BO_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
+  if (d->cand_kind == BO_CAND_GRID) {
+    long long total = 1;
+    for (int k = 0; k < d->dim; ++k) {
+      if (d->grid_shape[k] <= 0) return BO_ERR_ARG;
+      total *= d->grid_shape[k];
+    }
+    if (d->cand_offset < 0 || d->cand_offset + d->n_cand > total) return BO_ERR_ARG;
+  }
+  return BO_OK;
+}
 
-  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
-  d2* wpack = (d2*)ws;
-  double* alpha = (double*)(ws + pl.off_alpha);
-  double* xpad = (double*)(ws + pl.off_xpad);
-  double* xc = (double*)(ws + pl.off_xc);
-  double* excl = (double*)(ws + pl.off_excl);
-  TopEntry* partial = (TopEntry*)(ws + pl.off_partial);
-  int* sep_flag = (int*)(ws + pl.off_status + 16);
-  int* conv_flag = (int*)(ws + pl.off_status + 32);
-
-  FusedArgs fa;
+// Arguments of the fused kernels (every path's: the prep launch and the grid-convolution path copy from them);
+// ws is the aligned workspace.  Fails on a Sobol descriptor alone.
+static int fill_fused_args(const bo_predict_desc* d, const Plan& pl, char* ws, const double* kstar, long long ks_rows,
+                           FusedArgs& fa) {
   memset(&fa, 0, sizeof(fa));
   fa.n_obj = d->n_obj;
   fa.dim = d->dim;
@@ -781,30 +758,24 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     fa.grid_shape[k] = d->grid_shape[k] > 0 ? d->grid_shape[k] : 1;
   }
   if (d->cand_kind == BO_CAND_GRID) {
-    long long total = 1;
-    for (int k = 0; k < d->dim; ++k) {
-      if (d->grid_shape[k] <= 0) return BO_ERR_ARG;
-      total *= d->grid_shape[k];
-    }
-    if (d->cand_offset < 0 || d->cand_offset + d->n_cand > total) return BO_ERR_ARG;
     fa.idx32 = d->cand_offset + d->n_cand < (1LL << 31) ? 1 : 0;
     for (int k = 0; k < d->dim; ++k) fa.idx32 = fa.idx32 && d->grid_shape[k] < (1LL << 31);
   }
   fa.cand = d->cand;
   if (d->cand_kind == BO_CAND_SOBOL) {
     if (!d->cand) return BO_ERR_ARG;
-    st = bo_sobol_fill(&fa.sob, d->dim, (const bo_sobol_desc*)d->cand);
+    const int st = bo_sobol_fill(&fa.sob, d->dim, (const bo_sobol_desc*)d->cand);
     if (st != BO_OK) return st;
     if (d->cand_offset < 0 || (unsigned long long)(d->cand_offset + d->n_cand) > (1ull << fa.sob.bits))
       return BO_ERR_ARG;
   }
-  fa.xpad = xpad;
-  fa.xc = xc;
-  fa.excl = d->excl_points ? excl : nullptr;
+  fa.xpad = (double*)(ws + pl.off_xpad);
+  fa.xc = (double*)(ws + pl.off_xc);
+  fa.excl = d->excl_points ? (double*)(ws + pl.off_excl) : nullptr;
   fa.hkeys = (const unsigned long long*)(ws + pl.off_hash);
   fa.hidx = (const int*)(ws + pl.off_hash + (size_t)pl.hash_slots * 8);
   fa.hmask = pl.hash_slots - 1;
-  fa.wpack = wpack;
+  fa.wpack = (d2*)ws;
   fa.upper = (pl.cm && !(d->mode & BO_PREDICT_DENSE)) ? 1 : 0;
   fa.wpack_bytes = (unsigned int)((size_t)d->n_obj * pl.n_pad * pl.n_pad * sizeof(double));
   if (pl.cm) {
@@ -812,7 +783,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
     fa.w_pairs = (int)(cm_blocks(pl.n_pad / 32, fa.upper) * 4 * d->n_obj);
     fa.wpack_bytes = (unsigned int)((size_t)fa.w_pairs * 2048);
   }
-  fa.alpha = alpha;
+  fa.alpha = (double*)(ws + pl.off_alpha);
   for (int o = 0; o < d->n_obj; ++o) {
     fa.pm[o] = d->prior_mean[o];
     fa.pv[o] = d->prior_var[o];
@@ -829,11 +800,10 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   fa.std_var = d->std_var;
   fa.ucb = d->ucb;
   fa.acq = d->acq;
-  fa.partial = partial;
+  fa.partial = (TopEntry*)(ws + pl.off_partial);
   fa.kstar = kstar;
   fa.ks_rows = ks_rows;
-
-  fa.sep_flag = pl.sep ? sep_flag : nullptr;
+  fa.sep_flag = pl.sep ? (int*)(ws + pl.off_status + 16) : nullptr;
   fa.sep_S = pl.sep ? (int)d->grid_shape[d->dim - 1] : 1;
   fa.sep_lo = pl.sep ? d->grid_lo[d->dim - 1] : 0;
   fa.off_tbl = pl.off_tbl;
@@ -841,145 +811,145 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   fa.rw_cache = pl.rw_cache ? 1 : 0;
   fa.rw_stride = pl.rw_stride;
   fa.off_exp = pl.off_exp;
-  fa.conv_flag = pl.conv ? conv_flag : nullptr;
-  // the grid-convolution path's arguments and the schedule of its accumulate kernel: the prep launch's
-  // setup block writes the buckets, the tickets and the counters that the kernels behind it read
-  bo::ConvArgs ca;
-  bo::ConvSched csched;
-  memset(&csched, 0, sizeof(csched));
+  fa.conv_flag = pl.conv.planned ? (int*)(ws + pl.off_status + 32) : nullptr;
+  return BO_OK;
+}
+
+// Arguments of the grid-convolution path (planned): the call's, those it shares with the fused kernels, and its
+// workspace arrays at the offsets of the plan's layout.
+static void fill_conv_args(const bo_predict_desc* d, const Plan& pl, char* ws, const FusedArgs& fa, bo::ConvArgs& ca) {
+  const bo::ConvPlan& cp = pl.conv;
+  const bo::ConvLayout& L = cp.ws;
   memset(&ca, 0, sizeof(ca));
-  if (pl.conv) {
-    ca.n_obj = d->n_obj;
-    ca.n = (int)d->n_train;
-    ca.n_pad = pl.n_pad;
-    ca.R = (int)d->grid_shape[0];
-    ca.C = (int)d->grid_shape[1];
-    ca.lo0 = d->grid_lo[0];
-    ca.lo1 = d->grid_lo[1];
-    ca.cand_offset = d->cand_offset;
-    ca.n_cand = d->n_cand;
-    ca.ld_out = fa.ld_out;
-    ca.row_lo = pl.conv_row_lo;
-    ca.nrows = pl.conv_nrows;
-    ca.ldr = pl.conv_ldr;
-    ca.LT = pl.conv_LT;
-    ca.NP = pl.conv_NP;
-    ca.Cpad = pl.conv_Cpad;
-    ca.flag = conv_flag;
-    ca.x = d->x_train;
-    ca.kinv = d->kinv;
-    ca.ld_k = d->ld_k;
-    ca.alpha = alpha;
-    for (int o = 0; o < d->n_obj; ++o) {
-      ca.pm[o] = fa.pm[o];
-      ca.pv[o] = fa.pv[o];
-      ca.nhl[o] = fa.nhl[o];
-      ca.beta[o] = fa.beta[o];
-      ca.inv_rsq_pv[o] = fa.inv_rsq_pv[o];
-      ca.inv_pv[o] = fa.inv_pv[o];
-    }
-    ca.min_var = fa.min_var;
-    ca.cstart = (int*)(ws + pl.off_conv_ints);
-    ca.order = ca.cstart + (ca.C + 1);
-    ca.rc = ca.order + ca.n;
-    ca.pstart = ca.rc + 2 * ca.n;
-    ca.pkept = ca.pstart + ca.LT;
-    ca.clist = ca.pkept + ca.LT;
-    ca.ticket = (int*)(((uintptr_t)(ca.clist + (size_t)bo::kConvClasses * ca.LT) + 127) & ~(uintptr_t)127);
-    ca.ccount = ca.ticket + BO_MAX_OBJ * bo::kConvTicketGroups * bo::kConvTicketStride;
-    ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
-    ca.n_pairs = pl.conv_pairs;
-    ca.pair_sl = (int*)(ws + pl.off_conv_sl);
-    ca.pair_w = (double*)(ws + pl.off_conv_w);
-    ca.Tm = (double*)(ws + pl.off_conv_Tm);
-    ca.T = (double*)(ws + pl.off_conv_T);
-    ca.mu = d->mu;
-    ca.var = d->var;
-    ca.std_mu = d->std_mu;
-    ca.std_var = d->std_var;
-    ca.ucb = d->ucb;
-    ca.acq = d->acq;
-    ca.topq = d->topq;
-    ca.partial = partial;
-    ca.n_lists = pl.grid * pl.waves;
-    ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
-    ca.hkeys = fa.hkeys;
-    ca.hidx = fa.hidx;
-    ca.hmask = fa.hmask;
-    csched = bo::conv_acc_schedule(ca.R, ca.LT, ca.ldr, ca.n_obj, num_cus());
+  ca.n_obj = d->n_obj;
+  ca.n = (int)d->n_train;
+  ca.n_pad = pl.n_pad;
+  ca.R = (int)d->grid_shape[0];
+  ca.C = (int)d->grid_shape[1];
+  ca.lo0 = d->grid_lo[0];
+  ca.lo1 = d->grid_lo[1];
+  ca.cand_offset = d->cand_offset;
+  ca.n_cand = d->n_cand;
+  ca.ld_out = fa.ld_out;
+  ca.row_lo = cp.row_lo;
+  ca.nrows = cp.nrows;
+  ca.ldr = cp.ldr;
+  ca.LT = cp.LT;
+  ca.NP = cp.NP;
+  ca.Cpad = cp.Cpad;
+  ca.flag = (int*)fa.conv_flag;
+  ca.x = d->x_train;
+  ca.kinv = d->kinv;
+  ca.ld_k = d->ld_k;
+  ca.alpha = fa.alpha;
+  memcpy(ca.pm, fa.pm, sizeof(ca.pm));
+  memcpy(ca.pv, fa.pv, sizeof(ca.pv));
+  memcpy(ca.nhl, fa.nhl, sizeof(ca.nhl));
+  memcpy(ca.beta, fa.beta, sizeof(ca.beta));
+  memcpy(ca.inv_rsq_pv, fa.inv_rsq_pv, sizeof(ca.inv_rsq_pv));
+  memcpy(ca.inv_pv, fa.inv_pv, sizeof(ca.inv_pv));
+  ca.min_var = fa.min_var;
+  ca.cstart = (int*)(ws + L.cstart);
+  ca.order = (int*)(ws + L.order);
+  ca.rc = (int*)(ws + L.rc);
+  ca.pstart = (int*)(ws + L.pstart);
+  ca.pkept = (int*)(ws + L.pkept);
+  ca.clist = (int*)(ws + L.clist);
+  ca.ticket = (int*)(ws + L.ticket);
+  ca.ccount = (int*)(ws + L.ccount);
+  ca.Tm = (double*)(ws + L.Tm);
+  ca.T = (double*)(ws + L.T);
+  ca.pair_sl = (int*)(ws + L.pair_sl);
+  ca.pair_w = (double*)(ws + L.pair_w);
+  ca.n_pairs = (int)(d->n_train * (d->n_train + 1) / 2);
+  ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
+  ca.mu = fa.mu;
+  ca.var = fa.var;
+  ca.std_mu = fa.std_mu;
+  ca.std_var = fa.std_var;
+  ca.ucb = fa.ucb;
+  ca.acq = fa.acq;
+  ca.topq = d->topq;
+  ca.partial = fa.partial;
+  ca.n_lists = pl.grid * pl.waves;
+  ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
+  ca.hkeys = fa.hkeys;
+  ca.hidx = fa.hidx;
+  ca.hmask = fa.hmask;
+}
+
+// Arguments of the prep launch (but for the grid-convolution path's); returns the dynamic LDS bytes of its hash table.
+static size_t fill_prep_args(const bo_predict_desc* d, const Plan& pl, char* ws, bool kmem, const FusedArgs& fa,
+                             PrepArgs& pa) {
+  memset(&pa, 0, sizeof(pa));
+  pa.pack_mode = pl.fp32 ? 2 : (pl.cm ? 0 : 1);
+  pa.wpack = ws;
+  pa.kinv = d->kinv;
+  pa.ld_k = d->ld_k;
+  pa.upper = fa.upper;
+  pa.n = (int)d->n_train;
+  pa.n_pad = pl.n_pad;
+  pa.ns = pl.ns;
+  pa.n_obj = d->n_obj;
+  const long long total = pl.fp32 ? c32_blocks(pl.n_pad / 64) * 1024 * d->n_obj
+                        : pl.cm ? cm_blocks(pl.n_pad / 32, fa.upper) * 512 * d->n_obj
+                                : (long long)d->n_obj * pl.n_pad * pl.n_pad / 2;
+  pa.pack_blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+  pa.alpha_blocks = (int)(((long long)d->n_obj * pl.n_pad + 3) / 4);
+  pa.alpha = (double*)fa.alpha;
+  pa.y = d->y_train;
+  pa.ld_y = d->ld_y;
+  for (int o = 0; o < d->n_obj; ++o) pa.pm[o] = d->prior_mean[o];
+  pa.rows = kmem ? 0 : 1;
+  pa.xpad = (double*)fa.xpad;
+  pa.xc = (double*)fa.xc;
+  pa.x = d->x_train;
+  pa.dim = d->dim;
+  pa.DIM = pl.dim_pad;
+  pa.sep_flag = (int*)fa.sep_flag;
+  pa.sep_lo = fa.sep_lo;
+  pa.sep_S = fa.sep_S;
+  pa.excl = (double*)(ws + pl.off_excl);
+  pa.excl_in = d->excl_points;
+  pa.n_excl = (kmem || !d->excl_points) ? 0 : pl.n_excl;
+  pa.hkeys = (unsigned long long*)fa.hkeys;
+  pa.hidx = (int*)fa.hidx;
+  pa.hslots = pl.hash_slots;
+  pa.n_hash = (kmem || d->topq == 0) ? 0 : pl.n_excl;
+  pa.hash_lds = pa.n_hash > 0 && pl.hash_slots <= 2048 ? 1 : 0;     // <= 24 KiB of LDS
+  return pa.hash_lds ? (size_t)pl.hash_slots * 12 : 0;
+}
+
+static int predict_impl(const bo_predict_desc* d, const double* kstar, long long ks_rows,
+                        void* workspace, size_t ws_bytes, void* stream) {
+  const bool kmem = kstar != nullptr;
+  Plan pl;
+  int st = make_plan(d, &pl, true, kmem);
+  if (st != BO_OK) return st;
+  if ((st = validate_call(d, pl, kmem, workspace, ws_bytes)) != BO_OK) return st;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = (char*)(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+
+  FusedArgs fa;
+  if ((st = fill_fused_args(d, pl, ws, kstar, ks_rows, fa)) != BO_OK) return st;
+  PrepArgs pa;
+  size_t prep_lds = fill_prep_args(d, pl, ws, kmem, fa, pa);
+  const bo::ConvArgs& ca = pa.conv;
+  if (pl.conv.planned) {
+    // the path's arguments and the schedule of its accumulate kernel travel in PrepArgs: the prep launch's setup
+    // block writes the buckets, the tickets and the counters that the kernels behind it read
+    fill_conv_args(d, pl, ws, fa, pa.conv);
+    pa.sched = bo::conv_acc_schedule(ca.R, ca.LT, ca.ldr, ca.n_obj, num_cus());
+    const size_t setup_lds = bo::ConvSetupLds(ca.n, ca.C, 256).bytes;
+    if (setup_lds > prep_lds) prep_lds = setup_lds;
   }
-  {
-    PrepArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.pack_mode = pl.fp32 ? 2 : (pl.cm ? 0 : 1);
-    pa.wpack = wpack;
-    pa.kinv = d->kinv;
-    pa.ld_k = d->ld_k;
-    pa.upper = fa.upper;
-    pa.n = (int)d->n_train;
-    pa.n_pad = pl.n_pad;
-    pa.ns = pl.ns;
-    pa.n_obj = d->n_obj;
-    const long long total = pl.fp32 ? c32_blocks(pl.n_pad / 64) * 1024 * d->n_obj
-                          : pl.cm ? cm_blocks(pl.n_pad / 32, fa.upper) * 512 * d->n_obj
-                                  : (long long)d->n_obj * pl.n_pad * pl.n_pad / 2;
-    pa.pack_blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    pa.alpha_blocks = (int)(((long long)d->n_obj * pl.n_pad + 3) / 4);
-    pa.alpha = alpha;
-    pa.y = d->y_train;
-    pa.ld_y = d->ld_y;
-    for (int o = 0; o < d->n_obj; ++o) pa.pm[o] = d->prior_mean[o];
-    pa.rows = kmem ? 0 : 1;
-    pa.xpad = xpad;
-    pa.xc = xc;
-    pa.x = d->x_train;
-    pa.dim = d->dim;
-    pa.DIM = pl.dim_pad;
-    pa.sep_flag = pl.sep ? sep_flag : nullptr;
-    pa.sep_lo = fa.sep_lo;
-    pa.sep_S = fa.sep_S;
-    pa.conv_flag = pl.conv ? conv_flag : nullptr;
-    for (int k = 0; k < 2; ++k) {
-      pa.conv_lo[k] = d->grid_lo[k];
-      pa.conv_ext[k] = (int)d->grid_shape[k];
-    }
-    pa.excl = excl;
-    pa.excl_in = d->excl_points;
-    pa.n_excl = (kmem || !d->excl_points) ? 0 : pl.n_excl;
-    pa.hkeys = (unsigned long long*)fa.hkeys;
-    pa.hidx = (int*)fa.hidx;
-    pa.hslots = pl.hash_slots;
-    pa.n_hash = (kmem || d->topq == 0) ? 0 : pl.n_excl;
-    pa.hash_lds = pa.n_hash > 0 && pl.hash_slots <= 2048 ? 1 : 0;     // <= 24 KiB of LDS
-    size_t prep_lds = pa.hash_lds ? (size_t)pl.hash_slots * 12 : 0;
-    if (pl.conv) {
-      pa.conv_setup = 1;
-      pa.cs.x = d->x_train;
-      pa.cs.n = ca.n;
-      pa.cs.n_obj = ca.n_obj;
-      pa.cs.R = ca.R;
-      pa.cs.C = ca.C;
-      pa.cs.lo0 = ca.lo0;
-      pa.cs.lo1 = ca.lo1;
-      pa.cs.rc = ca.rc;
-      pa.cs.cstart = ca.cstart;
-      pa.cs.order = ca.order;
-      pa.cs.ticket = ca.ticket;
-      pa.cs.ccount = ca.ccount;
-      pa.cs.acc_wgs = csched.wgs;
-      pa.cs.ngrp = csched.ngrp;
-      // (the plan keeps conv_lds_setup within the 160 KiB)
-      const size_t setup_lds = bo::conv_lds_setup(ca.n, ca.C);
-      if (setup_lds > prep_lds) prep_lds = setup_lds;
-    }
-    if (prep_lds > 64 * 1024)
-      BO_CHECK_HIP(hipFuncSetAttribute((const void*)predict_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)prep_lds));
-    hipLaunchKernelGGL(predict_prep_kernel,
-                       dim3((unsigned)(2 + pa.conv_setup + pa.alpha_blocks + pa.pack_blocks)), dim3(256), prep_lds, s,
-                       pa);
-    BO_CHECK_HIP(hipGetLastError());
-  }
+  if (prep_lds > 64 * 1024)
+    BO_CHECK_HIP(hipFuncSetAttribute((const void*)predict_prep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     (int)prep_lds));
+  hipLaunchKernelGGL(predict_prep_kernel,
+                     dim3((unsigned)(2 + (pl.conv.planned ? 1 : 0) + pa.alpha_blocks + pa.pack_blocks)), dim3(256),
+                     prep_lds, s, pa);
+  BO_CHECK_HIP(hipGetLastError());
   if (d->n_cand == 0) {
     if (d->topq > 0) {
       BO_CHECK_HIP(hipMemsetAsync(d->top_idx, 0xff, sizeof(int64_t) * d->topq, s));
@@ -989,10 +959,10 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   hipError_t e;
   const bool timed = g_timer.on && g_timer.used + 2 <= (int)g_timer.ev.size();
   if (timed) timer_mark(s);
-  if (pl.conv) {
+  if (pl.conv.planned) {
     // the grid-convolution kernels and the chunk-major kernel are both enqueued; the device flag
     // lets one of them run (no host synchronisation: the call stays capturable)
-    if (bo::launch_gridconv(ca, pl.conv_grid, csched, s) != hipSuccess) return BO_ERR_HIP;
+    if (bo::launch_gridconv(ca, pl.conv.grid, pa.sched, s) != hipSuccess) return BO_ERR_HIP;
   }
   if (kmem) e = launch_kmem(pl, fa, s);
   else if (pl.fp32) switch (pl.dim_pad) {
@@ -1012,8 +982,8 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   if (d->topq > 0) {
     // q <= 4: the lean rounds merge (a lane per wave list, bo_select.hip); else the general one
     const long long nl = (long long)pl.grid * pl.waves;
-    if (!bo_launch_rounds_merge(partial, nl, d->topq, d->top_val, d->top_idx, s)) {
-      hipLaunchKernelGGL(bo_topq_merge_kernel, dim3(1), dim3(256), 0, s, partial, nl, d->topq, d->top_val,
+    if (!bo_launch_rounds_merge(fa.partial, nl, d->topq, d->top_val, d->top_idx, s)) {
+      hipLaunchKernelGGL(bo_topq_merge_kernel, dim3(1), dim3(256), 0, s, fa.partial, nl, d->topq, d->top_val,
                          (long long*)d->top_idx);
       BO_CHECK_HIP(hipGetLastError());
     }

@@ -13,6 +13,7 @@
 
 #include "bo_common.h"
 
+#include <assert.h>
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
@@ -82,7 +83,7 @@ struct ConvArgs {
   int LT;                                // tau extent 2C - 1 padded to 16 (rows of T)
   int NP;                                // n padded to 16 (rows of Tm)
   int Cpad;                              // C padded to the wave tile's 64 columns
-  const int* flag;                       // 0 => every training point is a grid point
+  int* flag;                             // 0 => every training point is a grid point (the prep launch writes it)
   const double* x;                       // [n][2] training points
   const double* kinv;                    // [n_obj][ld_k][ld_k]
   long long ld_k;
@@ -119,10 +120,14 @@ struct ConvArgs {
   unsigned int hmask;
 };
 
-constexpr int kConvTicketGroups = 32;    // tickets per objective
+// tickets per objective, each on a cache line of its own.  One ticket per objective made the accumulate kernel
+// as long as its atomics: ~25 ns each on one address from 8 XCDs, 6,000 of them at C3 (160 us)
+constexpr int kConvTicketGroups = 32;
 constexpr int kConvTicketStride = 32;    // ints between two tickets (one 128-byte line each)
-// the accumulate kernel's work order: the tau in classes of their kept pair count k, class =
-// 2 floor(log2 k) + (the bit below the leading one): half-octaves, at most 48 for k < 2^24
+// the accumulate kernel's work order: the tau that kept pairs, appended by their list waves to the list of their
+// class of the kept count k, 2 floor(log2 k) + (the bit below the leading one): half-octaves, at most 48 for
+// k < 2^24, and shard tau % kConvShards (400 to 630 tau share a class at C3, and their atomics on one address
+// would queue)
 constexpr int kConvClasses = 64;
 #ifndef BO_CONV_SHARDS
 #define BO_CONV_SHARDS 8                 // BO_BUILD_VARIANT=DEF_CONV_SHARDS=1: the A/B of DESIGN.md §9
@@ -139,13 +144,13 @@ struct ConvSched {
   int dyn;                               // 1: some wave takes a second item (tickets and class lists in use)
 };
 
-// Arguments of the setup block of the prep launch (conv_setup_block).
-struct ConvSetupArgs {
-  const double* x;                       // [n][2] training points
-  int n, n_obj, R, C;
-  long long lo0, lo1;
-  int *rc, *cstart, *order, *ticket, *ccount;   // as in ConvArgs
-  int acc_wgs, ngrp;                     // ConvSched
+// Dynamic LDS of conv_setup_block (ints): cnt[C + 1] | col[n] | part[threads / 64].  Like the layouts of the
+// three kernels in bo_gridconv.hip: the block carves its pointers from it, the launch takes its bytes.
+struct ConvSetupLds {
+  int col, part;
+  size_t bytes;
+  __host__ __device__ ConvSetupLds(int n, int C, int threads)
+      : col(C + 1), part(col + n), bytes((size_t)(part + threads / 64) * sizeof(int)) {}
 };
 
 // exclusive scan of v[0 .. len) in place over a workgroup of THREADS, also written to out (if given);
@@ -188,19 +193,19 @@ __device__ __forceinline__ void conv_scan(int* v, int len, int* part, int* out) 
 // (found by a ballot per bit of the column) take consecutive places from their column's running
 // place in LDS.  N / 64 steps of two LDS round trips, where ranking a point against every earlier one
 // took N^2 / THREADS comparisons per thread.
-// LDS (ints): cnt[C + 1] | col[n] | part[THREADS / 64]
 template <int THREADS>
-__device__ __forceinline__ void conv_setup_block(const ConvSetupArgs& a, int* lds) {
+__device__ __forceinline__ void conv_setup_block(const ConvArgs& a, const ConvSched& sc, int* lds) {
+  const ConvSetupLds L(a.n, a.C, THREADS);
   int* cnt = lds;
-  int* col = cnt + (a.C + 1);
-  int* part = col + a.n;
+  int* col = lds + L.col;
+  int* part = lds + L.part;
   const int tid = threadIdx.x, lane = tid & 63;
   for (int c = tid; c <= a.C; c += THREADS) cnt[c] = 0;
   // the first items of the accumulate kernel's waves are their own indices in their group
-  for (int t = tid; t < a.n_obj * a.ngrp; t += THREADS) {
-    const int g = t % a.ngrp;
-    a.ticket[(t / a.ngrp * kConvTicketGroups + g) * kConvTicketStride] =
-        (a.acc_wgs - g + a.ngrp - 1) / a.ngrp * kConvAccWaves;
+  for (int t = tid; t < a.n_obj * sc.ngrp; t += THREADS) {
+    const int g = t % sc.ngrp;
+    a.ticket[(t / sc.ngrp * kConvTicketGroups + g) * kConvTicketStride] =
+        (sc.wgs - g + sc.ngrp - 1) / sc.ngrp * kConvAccWaves;
   }
   for (int t = tid; t < kConvClasses * kConvShards; t += THREADS)
     a.ccount[t / kConvShards * kConvCountStride + t % kConvShards] = 0;
@@ -243,15 +248,54 @@ __device__ __forceinline__ void conv_setup_block(const ConvSetupArgs& a, int* ld
   }
 }
 
-// LDS bounds that the plan tests (the pair stage's kernels launch with less than conv_lds_pair;
-// conv_lds_setup covers conv_setup_block and is what the prep launch asks for it);
-// the accumulate kernel's schedule on `cus` compute units; launch of the sequence behind the prep
-// launch (pair list, accumulate, contraction): `grid` workgroups of the contraction
-size_t conv_lds_setup(int n, int C);
-size_t conv_lds_pair(int n, int R, int C);
-size_t conv_lds_contract(int n, int C);
+// Byte offsets of the grid-convolution path's workspace arrays (ConvArgs describes them), from `base`.  The one
+// description of that part of the workspace: the plan's total and every pointer of predict_impl come from it.
+struct ConvLayout {
+  size_t cstart, order, rc, pstart, pkept, clist, ticket, ccount, Tm, T, pair_sl, pair_w, end;
+};
+
+inline ConvLayout conv_layout(long long n, int n_obj, long long C, long long LT, long long NP, long long ldr,
+                              size_t base) {
+  size_t at = base;
+  auto take = [&at](long long count, size_t elem, size_t align) {
+    const size_t off = (at + align - 1) / align * align;
+    at = off + (size_t)count * elem;
+    return off;
+  };
+  const long long pairs = n * (n + 1) / 2;   // every pair n <= m has one tau, so the list's length is known here
+  ConvLayout L;
+  L.cstart = take(C + 1, sizeof(int), 256);
+  L.order = take(n, sizeof(int), sizeof(int));
+  L.rc = take(2 * n, sizeof(int), sizeof(int));
+  L.pstart = take(LT, sizeof(int), sizeof(int));
+  L.pkept = take(LT, sizeof(int), sizeof(int));
+  L.clist = take(kConvClasses * LT, sizeof(int), sizeof(int));
+  L.ticket = take(BO_MAX_OBJ * kConvTicketGroups * kConvTicketStride, sizeof(int), 128);
+  L.ccount = take(kConvClasses * kConvCountStride, sizeof(int), 128);
+  L.Tm = take(n_obj * NP * ldr, sizeof(double), 256);
+  L.T = take(n_obj * LT * ldr, sizeof(double), 256);
+  L.pair_sl = take(pairs, sizeof(int), 256);
+  L.pair_w = take(n_obj * pairs, sizeof(double), 256);
+  // callers and captured graphs hold workspaces of the size that earlier versions returned; those kept 128 spare
+  // bytes in front of the tickets, a 256-byte line more whenever the tickets start on one: padded to that size
+  L.end = take(0, 1, 256) + (L.ticket % 256 == 0 ? 256 : 0);
+  return L;
+}
+
+// Whether the kernels' LDS tables fit for (n, R, C): the plan's admission test.  The accumulate kernel's
+// schedule on `cus` compute units.  Launch of the sequence behind the prep launch (pair list, accumulate,
+// contraction): `grid` workgroups of the contraction.
+bool conv_lds_admits(int n, int R, int C, int Cpad, int LT, int NP);
 ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus);
 hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st);
+
+// The grid-convolution part of a plan: its dimensions (as in ConvArgs) and workspace layout.
+struct ConvPlan {
+  bool planned;          // taken when the device flag allows
+  int grid;              // the contraction kernel's workgroups (<= Plan::grid: it fills the same lists)
+  int row_lo, nrows, ldr, LT, NP, Cpad;
+  ConvLayout ws;
+};
 
 // Host-side plan of one bo_predict_acquire call (bo_predict.hip: make_plan).
 struct Plan {
@@ -271,11 +315,7 @@ struct Plan {
   int grid, waves;       // persistent grid, waves per workgroup
   long long n_tiles;
   size_t lds;
-  bool conv;             // grid-convolution path planned (taken when the device flag allows)
-  int conv_grid;         // its contraction kernel's workgroups (<= grid: it fills the same lists)
-  int conv_row_lo, conv_nrows, conv_ldr, conv_LT, conv_NP, conv_Cpad;
-  size_t off_conv_T, off_conv_Tm, off_conv_ints, off_conv_sl, off_conv_w;
-  int conv_pairs;        // n (n + 1) / 2
+  ConvPlan conv;         // grid-convolution path (bo_gridconv.hip)
 };
 
 // launch wrappers (one translation unit per padded dimension)

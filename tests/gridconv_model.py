@@ -15,8 +15,8 @@ from oracle import oracle_np as O
 MARGIN = 1.15           # bo_predict.hip: kConvMargin
 MAX_N = 4096            # kConvMaxN
 LDS_BYTES = 160 * 1024
-PAIR_CHUNK = 256        # bo_gridconv.hip: kPairChunk (per wave)
-PAIR_WAVES = 8          # kTauPerWg
+PAIR_CHUNK = 256        # bo_gridconv.hip: conv_lds_admits, the plan's frozen admission bound (the LDS of
+PAIR_WAVES = 8          # no kernel): 8 x 256 = 2048 doubles and as many ints beside the tables of R, C and n
 
 
 def conv_planned(shape, n, n_obj, offset=0, count=None, mode="auto"):
@@ -100,7 +100,7 @@ def model_predict(x, y, kinv, pm, pv, ls, betas, shape, lo, min_var=1e-10):
     r = (x[:, 0] - lo[0]).astype(np.int64)
     c = (x[:, 1] - lo[1]).astype(np.int64)
     assert ((r >= 0) & (r < R) & (c >= 0) & (c < C)).all()
-    order = np.argsort(c, kind="stable")                       # conv_setup_kernel
+    order = np.argsort(c, kind="stable")                       # conv_setup_block
     cstart = np.searchsorted(c[order], np.arange(C + 1))
     LT, NP, Cpad = -(-(2 * C - 1) // 16) * 16, -(-n // 16) * 16, -(-C // 64) * 64
     HB, R2 = Cpad + LT // 2, 2 * R

@@ -83,6 +83,13 @@ def test_workspace_size_queries():
     d.grid_shape[0] = d.grid_shape[1] = 1024
     ws = lib.bo_predict_workspace_size(d)
     assert ws >= 2 * 512 * 512 * 8
+    # the grid-convolution path is planned for this descriptor: its arrays come on top of the others'
+    d.mode = _lib.MODE_NO_GRID_CONV
+    ws_off = lib.bo_predict_workspace_size(d)
+    d.mode = _lib.MODE_GRID_CONV
+    ws_on = lib.bo_predict_workspace_size(d)
+    assert 0 < ws_off < ws_on and ws_off % 256 == 0 and ws_on % 256 == 0 and ws % 256 == 0
+    d.mode = 0
     d.topq = 49
     assert lib.bo_predict_workspace_size(d) == 0          # over BO_MAX_TOPQ
     d.topq, d.n_obj = 3, 9

@@ -1,5 +1,5 @@
 """GPU tests of the grid-convolution path's pair stage (bo_gridconv.hip: the schedule of
-conv_setup_kernel, conv_list_kernel, conv_acc_kernel): pair lists that sit in one tau, clustered
+conv_setup_block, conv_list_kernel, conv_acc_kernel): pair lists that sit in one tau, clustered
 points, several row blocks per tau with a ragged last one, the per-objective weights of the shared
 list, more items than waves (tickets, the sorted work order with one, two and three passes), and
 bit equality across calls, graph replays and shards (the ticket order is in no value).
