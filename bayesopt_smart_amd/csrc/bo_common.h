@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include "../../include/bo_amd.h"
@@ -450,6 +451,16 @@ static __global__ __launch_bounds__(256) void bo_topq_merge_kernel(const TopEntr
     }
   }
 }
+
+// An environment knob of the fit path (host): the variable's value, read ONCE per process at the
+// site's first call and copied, so later changes of the environment are not seen (tests run the
+// variants in child processes); nullptr when unset.  bo_env_is: set and equal to `value`.
+inline const char* bo_env_read(const char* name) {
+  const char* e = getenv(name);
+  return e ? strdup(e) : nullptr;
+}
+#define BO_ENV_ONCE(name) ([]() -> const char* { static const char* const v = bo_env_read(name); return v; }())
+inline bool bo_env_is(const char* e, const char* value) { return e && strcmp(e, value) == 0; }
 
 // invert_k's blocked LU path (bo_lu.hip), called by bo_invert_k (bo_fit.hip) once for all the
 // objectives whose Cholesky failed (out[b] / km[b], b < n_lu)

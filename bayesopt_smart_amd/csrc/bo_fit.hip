@@ -1,15 +1,25 @@
-// GP fit on device: compute_mll and invert_k on one blocked right-looking Cholesky, one kernel
-// launch per 32-column step.
+// GP fit on device: compute_mll and invert_k on one blocked right-looking Cholesky of an
+// augmented matrix, in 32-column steps.
 //
 //   bo_compute_mll  numba_kernels.py:152-235   sum over objectives of the GP marginal log
 //                   likelihood of K/pv + 1e-8 I with y centred on the prior mean and scaled by
 //                   its population std.
 //   bo_invert_k     numba_kernels.py:370-403   inv(K + 1e-6 I) per objective (the reference's
-//                   LAPACK gesv); Cholesky first, blocked LU with partial pivoting (LAPACK's
-//                   getrf row choice) for any objective whose Cholesky fails or whose K is not
-//                   symmetric.
+//                   LAPACK gesv).
 //
-// One factorisation serves both: the Cholesky of an AUGMENTED lower-triangular matrix
+// What runs, in this order (fit_run owns the choice, bo_fit_path_counts counts it):
+//   1. the persistent kernel, up to 48 column blocks (N <= 1536; BO_FIT_PERSIST_MAX_NBT): after
+//      fit_init_kernel ONE launch of fit_persist_kernel runs the whole factorisation as a task
+//      queue, the steps handing over through flag words (see "persistent factorisation" below);
+//   2. one launch per 32-column step (fit_step_kernel) above that, when BO_FIT_PATH=launches
+//      forces it, or as the rerun of a call whose persistent kernel gave up a wait (its abort
+//      word): the kernel boundary is the only synchronisation;
+//   3. for the inverse: Cholesky (with one Newton step, inv_refine_kernel), then for every
+//      objective whose Cholesky fails or whose K is not symmetric the blocked LU with partial
+//      pivoting (bo_lu.hip, LAPACK getrf's row choice; N <= bo_lu_max_n() = 2048), then above the
+//      LU's capacity Gauss-Jordan with partial pivoting (gj_inverse).
+//
+// One factorisation serves both entry points: the Cholesky of an AUGMENTED lower-triangular matrix
 //
 //        [ K    .  ]      factoring only the first n_p columns leaves     [ L          .          ]
 //    A = [ B    C  ]      (n_p = N padded to 32 with an identity block)   [ B L^-T     C - B K^-1 B^T ]
@@ -21,22 +31,21 @@
 //     is upper triangular: bottom row block b is structurally zero in column blocks < b, and C's
 //     tile (b, c) receives its first contribution at step b (no zero fill).
 //
-// A is COLUMN-major (element (i, j) at j * Na + i) and lives in the workspace.  Launch k (32-column
-// step k, one launch per step; the kernel boundary is the only synchronisation) runs two roles:
-//   * panel (column block k): every panel workgroup applies step k-1's update to the diagonal
-//     tile and to ITS 32-row slab (MFMA, 4 waves), then wave 0 factors the diagonal tile and
-//     solves its slab rows in the same register sweep -- lanes 0..31 hold the diagonal rows,
-//     lanes 32..63 the slab rows, one row per lane: column j's pivot is a v_readlane, its
+// A is COLUMN-major (element (i, j) at j * Na + i) and lives in the workspace (InvLayout /
+// MllLayout below are the one description of each workspace).  Step k, as launch k of the
+// launch-per-step path or as block k of the persistent kernel's queue, has two roles:
+//   * panel (column block k): one workgroup per 32-row slab below the diagonal tile applies step
+//     k-1's update to the diagonal tile and to ITS slab (MFMA, 4 waves), then factors the diagonal
+//     tile and solves its slab rows in the same register sweep -- lanes 0..31 hold the diagonal
+//     rows, lanes 32..63 the slab rows, one row per lane: column j's pivot is a v_readlane, its
 //     entries below the diagonal are both L_jj^-1 a_j for the tile and the triangular solve of
-//     the slab (X L_kk^T = A_pk), and the next column is updated first so that the chain per
-//     column is readlane -> rsqrt -> mul -> readlane -> fma.  Every panel workgroup factors the
-//     diagonal tile redundantly (no inter-workgroup hand-off inside the launch);
+//     the slab (X L_kk^T = A_pk).  Every panel workgroup factors the diagonal tile redundantly
+//     (no hand-off between the panels of a step).  The sweep runs on one wave (panel_role, the
+//     inverse's launch path) or with the columns split over the 4 waves (p_panel, elsewhere);
 //   * update (column blocks > k, and C for the inverse): A_pc -= L_p,k-1 L_c,k-1^T for every live
-//     32 x 32 tile, one tile per wave (32 v_mfma_f64_16x16x4_f64), applying step k-1 one launch
-//     late (lookahead: the panel of step k needs only its own column block).
-// The critical path per step is one panel: ~0.4 us of MFMA, a 32-column register factorisation
-// and the kernel boundary.  Round 2 used two launches per 64-column step with a 64-long serial
-// substitution chain on one wave (45 us per panel at N = 2048).
+//     32 x 32 tile, one tile per wave (32 v_mfma_f64_16x16x4_f64), applying step k-1 one step
+//     late (lookahead: the panel of step k needs only its own column block).  The counts and the
+//     decode of the tiles are the schedule functions below, shared by host and device.
 
 #include "bo_common.h"
 
@@ -61,9 +70,6 @@ constexpr int kStepStoreAux = 16;
 constexpr int kStepStoreAux = 0;
 #endif
 
-#if defined(BO_FIT_U8) && !defined(BO_FIT_NODEFER)
-#error "BO_FIT_U8 (8-byte tile accesses, A/B only) has no rank-64 form: build it with BO_FIT_NODEFER"
-#endif
 #ifdef BO_FIT_NODEFER
 constexpr bool kFitNoDefer = true;
 #else
@@ -146,6 +152,97 @@ __device__ __forceinline__ int tri_row(long long t) {
   return u;
 }
 
+// --------------------------------------------------------------------------- schedule
+// The counts of the blocked schedule, defined once: the host sizes its grids and the persistent
+// kernel's task list with them, the kernels decode their work index with them
+// (tests/test_fit_blocking_model.py and tests/test_fit_persist_model.py restate them in numpy).
+
+// fit_init_kernel: lower tiles of the K part; tiles per objective (those, then the bottom tiles
+// live in their column block); work workgroups (the tiles, then the MLL's var(y - pm) per objective)
+__host__ __device__ inline long long init_tri(const Geo& g) { return (long long)g.nbt * (g.nbt + 1) / 2; }
+__host__ __device__ inline long long init_tiles(const Geo& g) { return g.ident ? 2 * init_tri(g) : init_tri(g) + g.nbt; }
+__host__ __device__ inline long long init_work(const Geo& g) { return g.n_obj * init_tiles(g) + (g.ident ? 0 : g.n_obj); }
+
+// steps (launches / blocks of the task queue): the inverse has one more, the last update of C
+__host__ __device__ inline int p_steps(const Geo& g) { return g.ident ? g.nbt + 1 : g.nbt; }
+// panels of step k per objective: one per slab below the diagonal tile
+__host__ __device__ inline int p_npanel(const Geo& g, int k) { return k < g.nbt ? (g.ident ? g.nbt : g.nbt - k) : 0; }
+// tiles per objective of step k-1's update of column block k+1 alone (what the next panel needs)
+__host__ __device__ inline int p_n1(const Geo& g, int k) {
+  if (k < 1 || k + 1 >= g.nbt) return 0;
+  return g.ident ? g.nbt - 1 : g.nbt - k;
+}
+// Step k-1's trailing update, applied at step k.  L part (MLL and inverse): the column blocks
+// c = cb0 .. nbt-1, each with its row blocks [c, RB); numbered from the last column, whose count
+// is `base`:  S(u) = u base + u (u - 1) / 2.  C part (inverse): the tiles (b, cp), cp <= b < k.
+__host__ __device__ inline long long lpart_S(long long u, long long base) { return u * base + u * (u - 1) / 2; }
+__host__ __device__ inline long long upd_base(const Geo& g, int k) { return g.ident ? k + 1 : 2; }
+__host__ __device__ inline long long upd_TL(const Geo& g, int k, int cb0) {
+  const long long m = g.nbt - cb0;
+  return k >= 1 && m > 0 ? lpart_S(m, upd_base(g, k)) : 0;
+}
+__host__ __device__ inline long long upd_TC(const Geo& g, int k) { return k >= 1 && g.ident ? (long long)k * (k + 1) / 2 : 0; }
+// persistent kernel, block k: the update's tiles behind the panels (column blocks >= k+2, and C)
+__host__ __device__ inline void p_n2(const Geo& g, int k, long long& TL2, long long& TC) {
+  TL2 = upd_TL(g, k, k + 2);
+  TC = upd_TC(g, k);
+}
+// launch-per-step path, launch k: the update it carries (update_role's UPD: the MLL defers every
+// odd step's trailing update to the next launch) and its tile counts
+__host__ __device__ inline int step_upd(const Geo& g, int k) { return g.ident || kFitNoDefer ? 0 : (k & 1) ? 1 : 2; }
+__host__ __device__ inline void step_n(const Geo& g, int k, long long& TL, long long& TC) {
+  TL = step_upd(g, k) == 1 ? p_n1(g, k) : upd_TL(g, k, k + 1);
+  TC = upd_TC(g, k);
+}
+
+struct PTile {
+  int o, rb, cb;            // L part: row / column block; C part: b / cp
+  bool cpart, first;
+};
+
+// Tile i of step k-1's update of column block k+1 (p_n1 of them): the L rows below the diagonal
+// tile, then the inverse's live bottom blocks
+__device__ __forceinline__ PTile tile_next_col(const Geo& g, int k, int i) {
+  PTile tl;
+  tl.cb = k + 1;
+  tl.rb = (!g.ident || i < g.nbt - k - 1) ? k + 1 + i : g.nbt + (i - (g.nbt - k - 1));
+  tl.cpart = false;
+  tl.first = false;
+  return tl;
+}
+
+// Tile t of step k-1's update over TL L-part tiles, then the C part: row and column block, and
+// whether it is the tile's first contribution (C's tile (b, cp) is first written at step b).
+__device__ __forceinline__ PTile tile_decode(const Geo& g, int k, long long t, long long TL) {
+  PTile tl;
+  tl.cpart = t >= TL;
+  if (!tl.cpart) {
+    const long long base = upd_base(g, k);
+    const double bb = 2.0 * (double)base - 1.0;
+    long long u = (long long)((-bb + sqrt(bb * bb + 8.0 * (double)t)) * 0.5);
+    if (u < 0) u = 0;
+    while (lpart_S(u + 1, base) <= t) ++u;
+    while (lpart_S(u, base) > t) --u;
+    tl.cb = g.nbt - 1 - (int)u;
+    tl.rb = tl.cb + (int)(t - lpart_S(u, base));
+    tl.first = false;
+  } else {
+    t -= TL;
+    const int u = tri_row(t);
+    tl.cb = k - 1 - u;
+    tl.rb = tl.cb + (int)(t - (long long)u * (u + 1) / 2);
+    tl.first = tl.rb == k - 1;
+  }
+  return tl;
+}
+
+// first row and column of a tile in its objective's augmented matrix
+__device__ __forceinline__ void tile_origin(const Geo& g, const PTile& t, long long& row0, long long& col0) {
+  const long long off = t.cpart ? (long long)g.nbt * NB : 0;
+  row0 = off + (long long)t.rb * NB;
+  col0 = off + (long long)t.cb * NB;
+}
+
 // ------------------------------------------------------------------------------- init
 // Lower 32 x 32 tiles of the augmented matrix (one workgroup per tile, linear tile index over the
 // lower triangle of the K part, then the bottom tiles that are live in their column block).
@@ -166,13 +263,13 @@ __global__ __launch_bounds__(256) void fit_init_kernel(double* __restrict__ A, G
                                                        const double* __restrict__ x, int dim,
                                                        const double* __restrict__ y, long long ld_y,
                                                        FitParams p, double* __restrict__ part,
-                                                       int* __restrict__ status, int tiles_per_obj,
+                                                       int* __restrict__ status,
                                                        int* __restrict__ flags, long long n_flags) {
   __shared__ double tile[NB][NB + 1];
   __shared__ double red[256];
   const int tid = threadIdx.x;
   const long long np_ = (long long)g.nbt * NB;
-  const int work_blocks = g.n_obj * tiles_per_obj + (g.ident ? 0 : g.n_obj);
+  const int tiles_per_obj = (int)init_tiles(g), work_blocks = (int)init_work(g);
   if ((int)blockIdx.x >= work_blocks) {
     // the persistent factorisation's flag words (dequeue counter, panel flags, tile versions):
     // zeroed here, one launch before the kernel that polls them
@@ -204,7 +301,7 @@ __global__ __launch_bounds__(256) void fit_init_kernel(double* __restrict__ A, G
   }
   const int o = blockIdx.x / tiles_per_obj;
   long long t = blockIdx.x % tiles_per_obj;
-  const long long tri = (long long)g.nbt * (g.nbt + 1) / 2;
+  const long long tri = init_tri(g);
   int ti, tj;                                  // tile row / column block
   if (t < tri) {
     ti = tri_row(t);
@@ -451,10 +548,6 @@ __device__ __forceinline__ void panel_role(double* __restrict__ Ao, const Geo& g
   }
 }
 
-// L part (MLL and inverse): the column blocks c = k+1 .. nbt-1, each with its row blocks
-// [c, RB); numbered from the last column, whose count is `base`:  S(u) = u base + u (u - 1) / 2.
-__device__ __forceinline__ long long lpart_S(long long u, long long base) { return u * base + u * (u - 1) / 2; }
-
 // Update role of launch k: one 32 x 32 tile per wave.
 //   UPD 0: step k-1 on every column block >= k+1 (and the inverse's C part)
 //   UPD 1: step k-1 on column block k+1 only (the MLL's odd launches: what the next panel needs)
@@ -467,32 +560,11 @@ __device__ __forceinline__ void update_role(double* __restrict__ A, const Geo& g
   const long long per = TL + TC;
   if (wt >= per * g.n_obj) return;
   const int o = (int)(wt / per);
-  long long t = wt % per;
-  const long long np_ = (long long)g.nbt * NB;
+  const long long t = wt % per;
+  const PTile tl = UPD == 1 ? tile_next_col(g, k, (int)t) : tile_decode(g, k, t, TL);
+  const bool first = tl.first;
   long long row0, col0;
-  bool first = false;
-  if (UPD == 1) {
-    col0 = (long long)(k + 1) * NB;
-    row0 = (k + 1 + t) * NB;
-  } else if (t < TL) {
-    const long long base = g.ident ? k + 1 : 2;
-    const double bb = 2.0 * (double)base - 1.0;
-    long long u = (long long)((-bb + sqrt(bb * bb + 8.0 * (double)t)) * 0.5);
-    if (u < 0) u = 0;
-    while (lpart_S(u + 1, base) <= t) ++u;
-    while (lpart_S(u, base) > t) --u;
-    const long long c = g.nbt - 1 - u;
-    row0 = (c + (t - lpart_S(u, base))) * NB;
-    col0 = c * NB;
-  } else {
-    t -= TL;
-    const int u = tri_row(t);
-    const long long cp = k - 1 - u;
-    const long long b = cp + (t - (long long)u * (u + 1) / 2);
-    row0 = np_ + b * NB;
-    col0 = np_ + cp * NB;
-    first = b == k - 1;                          // C tile (b, cp): first contribution at step b
-  }
+  tile_origin(g, tl, row0, col0);
   double* Ao = A + (long long)o * g.ostride;
   const long long Na = g.Na;
   constexpr int R = UPD == 2 ? 2 : 1;                             // steps applied
@@ -501,7 +573,6 @@ __device__ __forceinline__ void update_role(double* __restrict__ A, const Geo& g
   const bool stamp_last = wt == per * g.n_obj - 1;
   if (stamp) FIT_STAMP(8);
   if (stamp_last) FIT_STAMP(10);
-#ifndef BO_FIT_U8
   // 16-byte accesses: the MFMA rows are interleaved (A-side m -> tile column 2 m + tb, B-side n ->
   // tile row 2 n + rb), so that each lane's two 16 x 16 blocks sit in adjacent doubles: every load
   // and store moves a double2 (the 8-byte forms run at 0.54-0.70x the 16-byte rate)
@@ -543,48 +614,6 @@ __device__ __forceinline__ void update_role(double* __restrict__ A, const Geo& g
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), tr, voff, (8 * i + tb) * col_bytes,
                                              kStepStoreAux);
     }
-#else
-  // the tile's current values first (one memory round trip with the operands)
-  double cv[2][2][4];
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        cv[tb][rb][i] = first ? 0.0 : Ao[(col0 + 16 * tb + lg + 4 * i) * Na + row0 + 16 * rb + li];
-  double av[2][8], bv[2][8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      av[h][ks] = Lp[(4 * ks + lg) * Na + col0 + 16 * h + li];
-      bv[h][ks] = Lp[(4 * ks + lg) * Na + row0 + 16 * h + li];
-    }
-  d4 acc[2][2];
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) acc[tb][rb] = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) acc[tb][rb] = mfma64(av[tb][ks], bv[rb][ks], acc[tb][rb]);
-  // D[t][r]: t = 16 tb + lg + 4 i (tile column), r = 16 rb + li (tile row)
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-      {
-        double* dst = Ao + (col0 + 16 * tb + lg + 4 * i) * Na + row0 + 16 * rb + li;
-        if constexpr (kStepStoreAux != 0) __hip_atomic_store(dst, cv[tb][rb][i] - acc[tb][rb][i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        else *dst = cv[tb][rb][i] - acc[tb][rb][i];
-      }
-#endif
 #ifdef BO_FIT_TIMING
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (stamp) FIT_STAMP(9);
@@ -902,9 +931,6 @@ __device__ __forceinline__ void st_flag(int* p, int v) {
 __device__ __forceinline__ double ld_sc1(const double* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-__device__ __forceinline__ void st_sc1(double* p, double v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // The calling wave waits until *fp >= want on every active lane (one flag per lane, all loads in
 // flight at once).  false on abort: the spin bound (~1 s) passed here or another wave gave up.
@@ -927,42 +953,15 @@ __device__ bool wave_wait(const int* fp, int want, bool active, int* abort_w) {
 // is structurally zero in column blocks < b)
 __device__ __forceinline__ int p_s0(const Geo& g, int rb) { return (g.ident && rb >= g.nbt) ? rb - g.nbt : 0; }
 
-__device__ __forceinline__ int p_n1(const Geo& g, int k) {      // tiles per objective of A_{k-1}[k+1]
-  if (k < 1 || k + 1 >= g.nbt) return 0;
-  return g.ident ? g.nbt - 1 : g.nbt - k;
-}
-__device__ __forceinline__ int p_npanel(const Geo& g, int k) { return k < g.nbt ? (g.ident ? g.nbt : g.nbt - k) : 0; }
-__device__ __forceinline__ void p_n2(const Geo& g, int k, long long& TL2, long long& TC) {
-  TL2 = 0;
-  TC = 0;
-  if (k < 1) return;
-  const long long m2 = g.nbt - k - 2, base = g.ident ? k + 1 : 2;
-  TL2 = m2 > 0 ? m2 * base + m2 * (m2 - 1) / 2 : 0;
-  TC = g.ident ? (long long)k * (k + 1) / 2 : 0;
-}
-
-struct PTile {
-  int o, rb, cb;            // L part: row / column block; C part: b / cp
-  bool cpart, first;
-};
-
 // One 32 x 32 tile of step s's trailing update on one wave (the update role's body with sc1
 // loads and stores).  Returns after the wave's stores are issued.
 __device__ __forceinline__ void p_tile_update(double* __restrict__ A, const Geo& g, int s, const PTile& t) {
   const int lane = threadIdx.x & 63, li = lane & 15, lg = lane >> 4;
-  const long long np_ = (long long)g.nbt * NB;
   long long row0, col0;
-  if (t.cpart) {
-    row0 = np_ + (long long)t.rb * NB;
-    col0 = np_ + (long long)t.cb * NB;
-  } else {
-    row0 = (long long)t.rb * NB;
-    col0 = (long long)t.cb * NB;
-  }
+  tile_origin(g, t, row0, col0);
   double* Ao = A + (long long)t.o * g.ostride;
   const long long Na = g.Na;
   const double* Lp = Ao + (long long)s * NB * Na;
-#ifndef BO_FIT_U8
   // 16-byte sc1 buffer loads and stores, rows interleaved as in update_role
   typedef double dv2 __attribute__((ext_vector_type(2)));
   const int col_bytes = (int)(Na * 8);
@@ -1002,42 +1001,6 @@ __device__ __forceinline__ void p_tile_update(double* __restrict__ A, const Geo&
       const dv2 v = {cv[tb][i].x - acc[tb][0][i], cv[tb][i].y - acc[tb][1][i]};
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4v, v), tr, voff_t, (8 * i + tb) * col_bytes, 16);
     }
-#else
-  double cv[2][2][4];
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        cv[tb][rb][i] = t.first ? 0.0 : ld_sc1(Ao + (col0 + 16 * tb + lg + 4 * i) * Na + row0 + 16 * rb + li);
-  double av[2][8], bv[2][8];
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      av[h][ks] = ld_sc1(Lp + (4 * ks + lg) * Na + col0 + 16 * h + li);
-      bv[h][ks] = ld_sc1(Lp + (4 * ks + lg) * Na + row0 + 16 * h + li);
-    }
-  d4 acc[2][2];
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb) acc[tb][rb] = (d4){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-    for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-      for (int rb = 0; rb < 2; ++rb) acc[tb][rb] = mfma64(av[tb][ks], bv[rb][ks], acc[tb][rb]);
-#pragma unroll
-  for (int tb = 0; tb < 2; ++tb)
-#pragma unroll
-    for (int rb = 0; rb < 2; ++rb)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-        st_sc1(Ao + (col0 + 16 * tb + lg + 4 * i) * Na + row0 + 16 * rb + li, cv[tb][rb][i] - acc[tb][rb][i]);
-#endif
 }
 
 // The panel of step k for slab sb = k + 1 + w of objective o, on the whole workgroup: step k-1's
@@ -1319,13 +1282,8 @@ __global__ __launch_bounds__(256, 2) void fit_persist_kernel(double* __restrict_
       const long long u = 4ll * r + wave;
       if (u < (long long)g.n_obj * n1) {
         have = true;
+        tl = tile_next_col(g, k, (int)(u % n1));
         tl.o = (int)(u / n1);
-        const int i = (int)(u % n1);
-        tl.cb = k + 1;
-        tl.cpart = false;
-        tl.first = false;
-        if (!g.ident) tl.rb = k + 1 + i;
-        else tl.rb = i < g.nbt - k - 1 ? k + 1 + i : g.nbt + (i - (g.nbt - k - 1));
       }
     } else {
       long long TL2, TC;
@@ -1334,30 +1292,8 @@ __global__ __launch_bounds__(256, 2) void fit_persist_kernel(double* __restrict_
       const long long u = 4ll * (r - T1 - nP) + wave;
       if (per > 0 && u < (long long)g.n_obj * per) {
         have = true;
+        tl = tile_decode(g, k, u % per, TL2);
         tl.o = (int)(u / per);
-        long long tt = u % per;
-        if (tt < TL2) {
-          const long long base = g.ident ? k + 1 : 2;
-          const double bb = 2.0 * (double)base - 1.0;
-          long long uu = (long long)((-bb + sqrt(bb * bb + 8.0 * (double)tt)) * 0.5);
-          if (uu < 0) uu = 0;
-          while (lpart_S(uu + 1, base) <= tt) ++uu;
-          while (lpart_S(uu, base) > tt) --uu;
-          const long long c = g.nbt - 1 - uu;
-          tl.cb = (int)c;
-          tl.rb = (int)(c + (tt - lpart_S(uu, base)));
-          tl.cpart = false;
-          tl.first = false;
-        } else {
-          tt -= TL2;
-          const int uu = tri_row(tt);
-          const int cp = k - 1 - uu;
-          const int b = cp + (int)(tt - (long long)uu * (uu + 1) / 2);
-          tl.rb = b;
-          tl.cb = cp;
-          tl.cpart = true;
-          tl.first = b == s;
-        }
       }
     }
     const bool tstamp = r == 0 && T1 > 0 && wave == 0;
@@ -1410,135 +1346,185 @@ Geo make_geo(int n, int n_obj, bool ident) {
   return g;
 }
 
-size_t geo_bytes(const Geo& g) { return a256((size_t)g.n_obj * g.ostride * sizeof(double)); }
+// ----------------------------------------------------------------------------- layouts
+// Byte offsets of each workspace's arrays, one line per array, and the total.  The
+// *_workspace_size functions return `total` and the entry points take every pointer from the same
+// struct.  Every array is padded to 256 bytes.  Callers cache the sizes, so the totals are part of
+// the ABI's behaviour (tests/fit_layout_model.py restates them).
+struct Carve {
+  size_t at = 0;
+  size_t operator()(size_t bytes) { const size_t off = at; at += a256(bytes); return off; }
+};
 
-// init launch + one launch per step (inverse: one more, the last step's update of C)
-int fit_factor(double* A, const Geo& g, const double* km, long long ld, const double* x, int dim,
-               const double* y, long long ld_y, const FitParams& p, double* part, int* status,
-               hipStream_t s) {
-  const long long tri = (long long)g.nbt * (g.nbt + 1) / 2;
-  const long long tiles = g.ident ? 2 * tri : tri + g.nbt;
-  const long long blocks = g.n_obj * tiles + (g.ident ? 0 : g.n_obj);
-  hipLaunchKernelGGL(fit_init_kernel, dim3((unsigned)blocks), dim3(256), 0, s, A, g, (double*)km, ld,
-                     x, dim, y, ld_y, p, part, status, (int)tiles, (int*)nullptr, 0ll);
+// The inverse's 512-byte status block, as ints: [0, BO_MAX_OBJ) the per-objective statuses (1: a
+// pivot was not positive, 2: K is not symmetric), then the named words.  The host reads back the
+// first kInvStatWords.
+constexpr int kInvStatGJ = BO_MAX_OBJ + 1;      // Gauss-Jordan met an exactly zero pivot
+constexpr int kInvStatAbort = BO_MAX_OBJ + 2;   // set by the persistent kernel when a wait gave up
+constexpr int kInvStatWords = BO_MAX_OBJ + 4;
+
+struct InvLayout { size_t A, bufA, bufB, piv, perm, status, flags, total; };
+InvLayout inv_layout(const Geo& g) {
+  Carve take;
+  const size_t gj = g.n > bo_lu_max_n() ? (size_t)g.n * g.n * sizeof(double) : 0;
+  InvLayout L;
+  L.A = take((size_t)g.n_obj * g.ostride * sizeof(double));   // augmented matrices (the LU batch reuses the region)
+  L.bufA = take(gj);                                          // Gauss-Jordan's matrix pair, n x n doubles each:
+  L.bufB = take(gj);                                          //   present only above bo_lu_max_n()
+  L.piv = take((size_t)g.n * sizeof(int));                    // Gauss-Jordan's pivot rows
+  L.perm = take((size_t)g.n * sizeof(int));                   //   and column permutation
+  L.status = take(512);                                       // the status block
+  L.flags = take((size_t)p_flag_words(g) * sizeof(int));      // the persistent kernel's flag words
+  L.total = take.at;
+  return L;
+}
+
+struct MllLayout { size_t A, spare, flags, total; };
+MllLayout mll_layout(const Geo& g) {
+  Carve take;
+  MllLayout L;
+  L.A = take((size_t)g.n_obj * g.ostride * sizeof(double));   // augmented matrices
+  // where the partials and statuses lived before they moved to pinned host memory, and 512 bytes
+  // behind them: unused, kept so that the total stays what callers cached
+  L.spare = take((size_t)g.n_obj * part_len(g) * sizeof(double) + BO_MAX_OBJ * sizeof(int));
+  take(512);
+  L.flags = take((size_t)p_flag_words(g) * sizeof(int));      // the persistent kernel's flag words
+  L.total = take.at;
+  return L;
+}
+
+// The MLL's pinned host block (unpadded): the kernels store into it with plain device stores and
+// the host reads it after the wait -- no status memset and no read-back copy per Powell evaluation.
+struct MllHost { size_t part, status, abort, done, total; };
+MllHost mll_host(const Geo& g) {
+  MllHost H;
+  H.part = 0;                                                            // n_obj x part_len doubles
+  H.status = H.part + (size_t)g.n_obj * part_len(g) * sizeof(double);    // n_obj ints
+  H.abort = H.status + (size_t)g.n_obj * sizeof(int);                    // a wait of the persistent kernel gave up
+  H.done = H.abort + sizeof(int);                                        // its completion word (host_poll)
+  H.total = H.done + sizeof(int);
+  return H;
+}
+
+// --------------------------------------------------------------------------- factorise
+// One factorisation: fit_init_kernel's inputs and where the kernels report.
+struct FitJob {
+  double* A;
+  Geo g;
+  const double *km, *x, *y;   // km: the inverse's input K, the MLL's kernel_matrix to rebuild; x, y: MLL only
+  long long ld, ld_y;
+  int dim;
+  FitParams p;
+  double* part;               // the MLL's partials
+  int *status, *flags;        // per-objective statuses; the persistent kernel's flag words,
+  int *habort, *hdone;        // its abort word and (for host_poll, or nullptr) its completion word
+};
+
+// fit_init_kernel; with `flags`, extra workgroups zero the persistent kernel's flag words
+int launch_init(const FitJob& j, int* flags, hipStream_t s) {
+  const long long nf = flags ? p_flag_words(j.g) : 0;
+  const long long grid = init_work(j.g) + (nf + 4095) / 4096;
+  hipLaunchKernelGGL(fit_init_kernel, dim3((unsigned)grid), dim3(256), 0, s, j.A, j.g, (double*)j.km, j.ld, j.x,
+                     j.dim, j.y, j.ld_y, j.p, j.part, j.status, flags, nf);
   BO_CHECK_HIP(hipGetLastError());
-  const int steps = g.ident ? g.nbt + 1 : g.nbt;
-  for (int k = 0; k < steps; ++k) {
-    const int n_panel = k < g.nbt ? (g.ident ? g.nbt : g.nbt - k) : 0;
-    // the MLL defers every odd step's trailing update to the next launch (UPD 1 / 2 above)
-    const int upd_kind = g.ident || kFitNoDefer ? 0 : (k & 1) ? 1 : 2;
-    long long TL = 0, TC = 0;
-    if (k >= 1) {
-      const long long m = g.nbt - 1 - k;
-      const long long base = g.ident ? k + 1 : 2;
-      TL = m > 0 ? m * base + m * (m - 1) / 2 : 0;
-      TC = g.ident ? (long long)k * (k + 1) / 2 : 0;
-      if (upd_kind == 1) TL = k + 1 < g.nbt ? g.nbt - k : 0;      // tiles (k+1 .. nbt, k+1)
-    }
-    const long long upd = ((TL + TC) * g.n_obj + 3) / 4;
-    const long long grid = (long long)g.n_obj * n_panel + upd;
+  return BO_OK;
+}
+
+// init launch + one launch per step
+int fit_factor(const FitJob& j, hipStream_t s) {
+  const Geo& g = j.g;
+  const int st = launch_init(j, nullptr, s);
+  if (st != BO_OK) return st;
+  for (int k = 0; k < p_steps(g); ++k) {
+    const int n_panel = p_npanel(g, k), upd = step_upd(g, k);
+    long long TL, TC;
+    step_n(g, k, TL, TC);
+    const long long grid = (long long)g.n_obj * n_panel + ((TL + TC) * g.n_obj + 3) / 4;
     if (grid == 0) continue;
-    if (g.ident)
-      hipLaunchKernelGGL((fit_step_kernel<false, 0>), dim3((unsigned)grid), dim3(256), 0, s, A, g, k, n_panel, TL, TC,
-                         part, status);
-    else if (upd_kind == 0)
-      hipLaunchKernelGGL((fit_step_kernel<true, 0>), dim3((unsigned)grid), dim3(256), 0, s, A, g, k, n_panel, TL, TC,
-                         part, status);
-    else if (upd_kind == 1)
-      hipLaunchKernelGGL((fit_step_kernel<true, 1>), dim3((unsigned)grid), dim3(256), 0, s, A, g, k, n_panel, TL, TC,
-                         part, status);
-    else
-      hipLaunchKernelGGL((fit_step_kernel<true, 2>), dim3((unsigned)grid), dim3(256), 0, s, A, g, k, n_panel, TL, TC,
-                         part, status);
+    auto step = g.ident ? fit_step_kernel<false, 0> : upd == 0 ? fit_step_kernel<true, 0> :
+                upd == 1 ? fit_step_kernel<true, 1> : fit_step_kernel<true, 2>;
+    hipLaunchKernelGGL(step, dim3((unsigned)grid), dim3(256), 0, s, j.A, g, k, n_panel, TL, TC, j.part, j.status);
   }
   return hipGetLastError() == hipSuccess ? BO_OK : BO_ERR_HIP;
 }
 
 // BO_FIT_TEST_ABORT=1 (tests only): every persistent launch raises its abort word at once, so
 // that the host's rerun on the launch-per-step path runs (tests/test_gpu_fit_abort.py)
-bool test_abort_enabled() {
-  static const int on = [] {
-    const char* e = getenv("BO_FIT_TEST_ABORT");
-    return (e && strcmp(e, "1") == 0) ? 1 : 0;
-  }();
-  return on != 0;
-}
+bool test_abort_enabled() { return bo_env_is(BO_ENV_ONCE("BO_FIT_TEST_ABORT"), "1"); }
 
-// The persistent path: init launch (which also zeroes the flag words) + ONE fit_persist_kernel
-// launch.  BO_ERR_UNSUPPORTED when the task list exceeds PMAX_STEPS blocks (the caller uses
-// fit_factor).  *habort (host-visible) is set when a wait gave up: the caller reruns fit_factor.
 // the largest column-block count the persistent schedule takes (BO_FIT_PERSIST_MAX_NBT overrides):
 // at N = 2048 (64 blocks) the launch-per-step schedule measured faster (r04c: MLL 0.99 vs 1.06 ms,
 // inverse 1.76 vs 2.38 ms) -- there the trailing update's throughput, not the panel chain, sets
 // the time, and the one-atomic task queue serialises ~13k dequeues
 int persist_max_nbt() {
-  static const int v = [] {
-    const char* e = getenv("BO_FIT_PERSIST_MAX_NBT");
-    return e ? atoi(e) : 48;
-  }();
-  return v;
+  const char* e = BO_ENV_ONCE("BO_FIT_PERSIST_MAX_NBT");
+  return e ? atoi(e) : 48;
 }
 
-int fit_factor_persist(double* A, const Geo& g, const double* km, long long ld, const double* x, int dim,
-                       const double* y, long long ld_y, const FitParams& p, double* part, int* status,
-                       int* flags, int* habort, hipStream_t s, int* hdone = nullptr) {
-  const int steps = g.ident ? g.nbt + 1 : g.nbt;
-  if (steps > PMAX_STEPS || g.nbt > persist_max_nbt()) return BO_ERR_UNSUPPORTED;
+// The persistent path: init launch (which also zeroes the flag words) + ONE fit_persist_kernel
+// launch.  BO_ERR_UNSUPPORTED when the task list exceeds PMAX_STEPS blocks or the column blocks
+// persist_max_nbt().  *j.habort is set when a wait gave up.
+int fit_factor_persist(const FitJob& j, hipStream_t s) {
+  const Geo& g = j.g;
+  if (p_steps(g) > PMAX_STEPS || g.nbt > persist_max_nbt()) return BO_ERR_UNSUPPORTED;
   PPlan pl;
   memset(&pl, 0, sizeof(pl));
-  pl.steps = steps;
+  pl.steps = p_steps(g);
   pl.force_abort = test_abort_enabled() ? 1 : 0;
   long long tot = 0;
-  for (int k = 0; k < steps; ++k) {
+  for (int k = 0; k < pl.steps; ++k) {
     pl.blk[k] = (int)tot;
-    const long long n1 = (k >= 1 && k + 1 < g.nbt) ? (g.ident ? g.nbt - 1 : g.nbt - k) : 0;
-    const long long np = k < g.nbt ? (g.ident ? g.nbt : g.nbt - k) : 0;
-    long long TL2 = 0, TC = 0;
-    if (k >= 1) {
-      const long long m2 = g.nbt - k - 2, base = g.ident ? k + 1 : 2;
-      TL2 = m2 > 0 ? m2 * base + m2 * (m2 - 1) / 2 : 0;
-      TC = g.ident ? (long long)k * (k + 1) / 2 : 0;
-    }
-    tot += (g.n_obj * n1 + 3) / 4 + g.n_obj * np + (g.n_obj * (TL2 + TC) + 3) / 4;
+    long long TL2, TC;
+    p_n2(g, k, TL2, TC);
+    tot += (g.n_obj * p_n1(g, k) + 3) / 4 + g.n_obj * p_npanel(g, k) + (g.n_obj * (TL2 + TC) + 3) / 4;
   }
   if (tot >= (1ll << 30)) return BO_ERR_UNSUPPORTED;
-  pl.blk[steps] = (int)tot;
+  pl.blk[pl.steps] = (int)tot;
   pl.total = (int)tot;
-  const long long tri = (long long)g.nbt * (g.nbt + 1) / 2;
-  const long long tiles = g.ident ? 2 * tri : tri + g.nbt;
-  const long long work = g.n_obj * tiles + (g.ident ? 0 : g.n_obj);
-  const long long nf = p_flag_words(g);
-  const long long zb = (nf + 4095) / 4096;
-  hipLaunchKernelGGL(fit_init_kernel, dim3((unsigned)(work + zb)), dim3(256), 0, s, A, g, (double*)km, ld, x, dim,
-                     y, ld_y, p, part, status, (int)tiles, flags, nf);
-  BO_CHECK_HIP(hipGetLastError());
+  const int st = launch_init(j, j.flags, s);
+  if (st != BO_OK) return st;
   const unsigned grid = (unsigned)(tot < 256 ? tot : 256);
-  hipLaunchKernelGGL(fit_persist_kernel, dim3(grid), dim3(256), 0, s, A, g, pl, flags, part, status, habort, hdone);
+  hipLaunchKernelGGL(fit_persist_kernel, dim3(grid), dim3(256), 0, s, j.A, g, pl, j.flags, j.part, j.status, j.habort,
+                     j.hdone);
   return hipGetLastError() == hipSuccess ? BO_OK : BO_ERR_HIP;
 }
 
-size_t flag_bytes(const Geo& g) { return a256((size_t)p_flag_words(g) * sizeof(int)); }
-
-// BO_FIT_PATH=launches forces the launch-per-step path (A/B measurements); read once
-bool persist_enabled() {
-  static const int on = [] {
-    const char* e = getenv("BO_FIT_PATH");
-    return (e && strcmp(e, "launches") == 0) ? 0 : 1;
-  }();
-  return on != 0;
-}
+// BO_FIT_PATH=launches forces the launch-per-step path (A/B measurements)
+bool persist_enabled() { return !bo_env_is(BO_ENV_ONCE("BO_FIT_PATH"), "launches"); }
 long long g_fit_paths[3];     // persistent, launch-per-step, persistent aborted -> rerun
+
+// The one owner of the path policy.  It tries the persistent kernel; on its abort word, on
+// BO_ERR_UNSUPPORTED, or when the launch-per-step path is forced, it runs fit_factor.  The two
+// entry points supply what differs: clear() zeroes their status words before a factorisation is
+// enqueued; wait(persistent, aborted) enqueues what follows it, awaits completion and reads the
+// abort word (after an abort the statuses are incomplete: the rerun redoes the whole call).
+template <class Clear, class Wait>
+int fit_run(const FitJob& j, hipStream_t s, Clear clear, Wait wait) {
+  auto count = [](int path) { __atomic_fetch_add(&g_fit_paths[path], 1, __ATOMIC_RELAXED); };
+  bool done = false, aborted = false;
+  int st;
+  if (persist_enabled()) {
+    if ((st = clear()) != BO_OK) return st;
+    st = fit_factor_persist(j, s);
+    if (st == BO_OK) {
+      if ((st = wait(true, aborted)) != BO_OK) return st;
+      done = !aborted;
+      count(done ? 0 : 2);
+    } else if (st != BO_ERR_UNSUPPORTED) {
+      return st;
+    }
+  }
+  if (done) return BO_OK;
+  count(1);
+  if ((st = clear()) != BO_OK) return st;
+  if ((st = fit_factor(j, s)) != BO_OK) return st;
+  return wait(false, aborted);
+}
 
 // The MLL's wait for the persistent kernel: poll the completion word it stores in pinned memory
 // (BO_FIT_HOSTWAIT=sync: the stream synchronisation instead).  false when the word did not come
 // within ~0.5 s (the caller then synchronises the stream, which reports any fault).
-bool host_poll_enabled() {
-  static const int on = [] {
-    const char* e = getenv("BO_FIT_HOSTWAIT");
-    return (e && strcmp(e, "sync") == 0) ? 0 : 1;
-  }();
-  return on != 0;
-}
+bool host_poll_enabled() { return !bo_env_is(BO_ENV_ONCE("BO_FIT_HOSTWAIT"), "sync"); }
 bool host_poll(const int* hdone) {
   const auto t0 = std::chrono::steady_clock::now();
   for (unsigned i = 0;; ++i) {
@@ -1552,13 +1538,7 @@ bool host_poll(const int* hdone) {
 long long g_inv_paths[3];     // Cholesky, blocked LU, Gauss-Jordan
 
 // BO_INV_REFINE=0 leaves the Cholesky-path inverse unrefined (A/B measurements only)
-bool refine_enabled() {
-  static const int on = [] {
-    const char* e = getenv("BO_INV_REFINE");
-    return (e && strcmp(e, "0") == 0) ? 0 : 1;
-  }();
-  return on != 0;
-}
+bool refine_enabled() { return !bo_env_is(BO_ENV_ONCE("BO_INV_REFINE"), "0"); }
 
 // The Cholesky path's result: -C mirrored into X (the dead first columns of each objective's
 // augmented matrix), then one Newton step X + X (I - (K + jitter I) X) into `out`
@@ -1599,16 +1579,103 @@ void* pinned(size_t bytes) {
   return buf;
 }
 
+// The inverse's Cholesky attempt for all objectives: factorise (fit_run), finish, read the
+// statuses back.  fail[o] != 0: objective o goes on to the LU path.
+int inv_cholesky(double* out, const FitJob& j, int* fail, hipStream_t s) {
+  const Geo& g = j.g;
+  int* hstat = (int*)pinned(sizeof(int) * kInvStatWords);
+  if (!hstat) return BO_ERR_HIP;
+  auto clear = [&]() -> int {
+    BO_CHECK_HIP(hipMemsetAsync(j.status, 0, 256, s));
+    return BO_OK;
+  };
+  auto wait = [&](bool persistent, bool& aborted) -> int {
+    const int st = inv_finish(out, j.A, g, j.km, j.ld, j.p.jitter, j.status, s);
+    if (st != BO_OK) return st;
+    BO_CHECK_HIP(hipMemcpyAsync(hstat, j.status, sizeof(int) * (persistent ? kInvStatWords : g.n_obj),
+                                hipMemcpyDeviceToHost, s));
+    BO_CHECK_HIP(hipStreamSynchronize(s));
+    aborted = persistent && hstat[kInvStatAbort] != 0;
+    return BO_OK;
+  };
+  const int st = fit_run(j, s, clear, wait);
+  if (st != BO_OK) return st;
+  for (int o = 0; o < g.n_obj; ++o) {
+    fail[o] = hstat[o];
+    if (!fail[o]) __atomic_fetch_add(&g_inv_paths[0], 1, __ATOMIC_RELAXED);
+  }
+  return BO_OK;
+}
+
+// LU path for the objectives whose Cholesky failed or whose K is not symmetric: the blocked LU
+// with partial pivoting of bo_lu.hip, all of them in one launch sequence, in the (now free)
+// augmented-matrix region.  Clears fail[] when it ran; above its capacity (N > 2048) it leaves
+// them to Gauss-Jordan.
+int inv_lu_batch(double* out, const double* km, long long ld, int n_obj, long long n, double jitter, void* region,
+                 size_t region_bytes, int* fail, hipStream_t s) {
+  double* lu_out[BO_MAX_OBJ];
+  const double* lu_km[BO_MAX_OBJ];
+  int n_lu = 0;
+  for (int o = 0; o < n_obj; ++o)
+    if (fail[o]) { lu_out[n_lu] = out + (long long)o * n * n; lu_km[n_lu] = km + (long long)o * ld * ld; ++n_lu; }
+  if (n_lu == 0 || n > bo_lu_max_n() || region_bytes < bo_lu_workspace_size(n, n_lu)) return BO_OK;
+  const int st = bo_lu_inverse(lu_out, lu_km, n_lu, ld, n, jitter, region, region_bytes, s);
+  __atomic_fetch_add(&g_inv_paths[1], n_lu, __ATOMIC_RELAXED);
+  if (st != BO_OK) return st;
+  for (int o = 0; o < n_obj; ++o) fail[o] = 0;
+  return BO_OK;
+}
+
+// Gauss-Jordan with partial pivoting for objective o: n step launches between the matrix pair,
+// the column permutation composed on the host, then the gather into `out` (objective o's block).
+int gj_inverse(double* out, const double* km, long long ld, long long n, int o, double jitter, double* bufA,
+               double* bufB, int* piv, int* perm, int* gstat, hipStream_t s) {
+  BO_CHECK_HIP(hipMemsetAsync(gstat, 0, sizeof(int), s));
+  const long long total = (long long)n * n;
+  hipLaunchKernelGGL(jitter_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     bufA, km, (long long)ld, (int)n, o, jitter);
+  BO_CHECK_HIP(hipGetLastError());
+  const int tiles = (int)((n + GJ_TILE - 1) / GJ_TILE);
+  const size_t col_lds = (size_t)n * sizeof(double);
+  if (col_lds > 64 * 1024)
+    BO_CHECK_HIP(hipFuncSetAttribute((const void*)gj_step_kernel,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)col_lds));
+  double* src = bufA;
+  double* dst = bufB;
+  for (int k = 0; k < n; ++k) {
+    hipLaunchKernelGGL(gj_step_kernel, dim3(tiles, tiles), dim3(256), col_lds, s, dst, src, (int)n,
+                       k, piv, gstat);
+    double* t = src; src = dst; dst = t;
+  }
+  BO_CHECK_HIP(hipGetLastError());
+  std::vector<int> hpiv((size_t)n);
+  int gs = 0;
+  BO_CHECK_HIP(hipMemcpyAsync(hpiv.data(), piv, sizeof(int) * n, hipMemcpyDeviceToHost, s));
+  BO_CHECK_HIP(hipMemcpyAsync(&gs, gstat, sizeof(int), hipMemcpyDeviceToHost, s));
+  BO_CHECK_HIP(hipStreamSynchronize(s));
+  if (gs) return BO_ERR_SINGULAR;
+  // column permutation: apply swaps (k, piv[k]) for k = n-1 .. 0 to the identity ordering
+  std::vector<int> hperm((size_t)n);
+  for (int j = 0; j < n; ++j) hperm[j] = j;
+  for (long long k = n - 1; k >= 0; --k) {
+    const int pk = hpiv[k];
+    const int t = hperm[k]; hperm[k] = hperm[pk]; hperm[pk] = t;
+  }
+  BO_CHECK_HIP(hipMemcpyAsync(perm, hperm.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(gather_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
+                     out + (long long)o * n * n, src, perm, (int)n);
+  BO_CHECK_HIP(hipGetLastError());
+  BO_CHECK_HIP(hipStreamSynchronize(s));
+  return BO_OK;
+}
+
 }  // namespace
 
 extern "C" {
 
 size_t bo_invert_k_workspace_size(int32_t n_obj, int64_t n) {
   if (n_obj < 1 || n < 1) return 0;
-  const Geo g = make_geo((int)n, n_obj, true);
-  // Gauss-Jordan scratch only above the blocked LU's capacity (the LU reuses the augmented region)
-  const size_t lu = n > bo_lu_max_n() ? 2 * a256((size_t)n * n * sizeof(double)) : 0;
-  return geo_bytes(g) + lu + 2 * a256((size_t)n * sizeof(int)) + 512 + flag_bytes(g);
+  return inv_layout(make_geo((int)n, n_obj, true)).total;
 }
 
 int bo_invert_k(double* out, const double* km, int64_t ld, int32_t n_obj, int64_t n, void* ws,
@@ -1627,125 +1694,41 @@ int bo_invert_k_ex(double* out, const double* km, int64_t ld, int32_t n_obj, int
   if (n > (1 << 15)) return BO_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < bo_invert_k_workspace_size(n_obj, n)) return BO_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const Geo g = make_geo((int)n, n_obj, true);
   char* w = (char*)ws;
-  double* A = (double*)w;
-  char* lu = w + geo_bytes(g);
-  const size_t gj = n > bo_lu_max_n() ? a256((size_t)n * n * sizeof(double)) : 0;
-  double* bufA = (double*)lu;
-  double* bufB = (double*)(lu + gj);
-  int* piv = (int*)(lu + 2 * gj);
-  int* perm = piv + a256((size_t)n * sizeof(int)) / sizeof(int);
-  int* status = (int*)(lu + 2 * gj + 2 * a256((size_t)n * sizeof(int)));
-  int* flags = (int*)(lu + 2 * gj + 2 * a256((size_t)n * sizeof(int)) + 512);
-  int* dabort = status + BO_MAX_OBJ + 2;          // set by the persistent kernel when a wait gave up
-  FitParams p;
-  memset(&p, 0, sizeof(p));
-  p.jitter = jitter;
-  int fail[BO_MAX_OBJ], path[BO_MAX_OBJ];
+  FitJob j;
+  memset(&j, 0, sizeof(j));
+  j.g = make_geo((int)n, n_obj, true);
+  const InvLayout L = inv_layout(j.g);
+  j.A = (double*)(w + L.A);
+  j.km = km;
+  j.ld = ld;
+  j.p.jitter = jitter;
+  j.status = (int*)(w + L.status);
+  j.flags = (int*)(w + L.flags);
+  j.habort = j.status + kInvStatAbort;
+  // Cholesky, unless it failed for every objective last time (the caller's hint): no doomed attempt
+  int fail[BO_MAX_OBJ];
   bool all_lu = lu_hint != nullptr;
   for (int o = 0; o < n_obj; ++o) {
-    path[o] = 0;
+    fail[o] = 1;
     if (all_lu && lu_hint[o] == 0) all_lu = false;
   }
-  if (all_lu) {
-    // every objective's Cholesky failed last time (the caller's hint): no doomed attempt
-    for (int o = 0; o < n_obj; ++o) fail[o] = 1;
-  } else {
-  int* hstat = (int*)pinned(sizeof(int) * (BO_MAX_OBJ + 4));
-  if (!hstat) return BO_ERR_HIP;
-  bool done = false;
-  if (persist_enabled()) {
-    BO_CHECK_HIP(hipMemsetAsync(status, 0, 256, s));
-    const int st = fit_factor_persist(A, g, km, ld, nullptr, 0, nullptr, 0, p, nullptr, status, flags, dabort, s);
-    if (st == BO_OK) {
-      // after an abort the statuses are incomplete: the rerun below redoes the whole call
-      const int st_f = inv_finish(out, A, g, km, ld, jitter, status, s);
-      if (st_f != BO_OK) return st_f;
-      BO_CHECK_HIP(hipMemcpyAsync(hstat, status, sizeof(int) * (BO_MAX_OBJ + 4), hipMemcpyDeviceToHost, s));
-      BO_CHECK_HIP(hipStreamSynchronize(s));
-      done = hstat[BO_MAX_OBJ + 2] == 0;
-      __atomic_fetch_add(&g_fit_paths[done ? 0 : 2], 1, __ATOMIC_RELAXED);
-    } else if (st != BO_ERR_UNSUPPORTED) {
-      return st;
-    }
-  }
-  if (!done) {
-    __atomic_fetch_add(&g_fit_paths[1], 1, __ATOMIC_RELAXED);
-    BO_CHECK_HIP(hipMemsetAsync(status, 0, 256, s));
-    int st = fit_factor(A, g, km, ld, nullptr, 0, nullptr, 0, p, nullptr, status, s);
-    if (st != BO_OK) return st;
-    const int st_f = inv_finish(out, A, g, km, ld, jitter, status, s);
-    if (st_f != BO_OK) return st_f;
-    BO_CHECK_HIP(hipMemcpyAsync(hstat, status, sizeof(int) * n_obj, hipMemcpyDeviceToHost, s));
-    BO_CHECK_HIP(hipStreamSynchronize(s));
-  }
-  for (int o = 0; o < n_obj; ++o) {
-    fail[o] = hstat[o];
-    if (!fail[o]) __atomic_fetch_add(&g_inv_paths[0], 1, __ATOMIC_RELAXED);
-  }
-  }   // Cholesky attempt
+  int st = all_lu ? BO_OK : inv_cholesky(out, j, fail, s);
+  if (st != BO_OK) return st;
+  // path bookkeeping: 0 Cholesky, 1 LU, 2 Gauss-Jordan (what the LU batch left)
+  int path[BO_MAX_OBJ];
   for (int o = 0; o < n_obj; ++o) path[o] = fail[o] ? 1 : 0;
-  // LU path for the objectives whose Cholesky failed or whose K is not symmetric: the blocked
-  // LU with partial pivoting of bo_lu.hip, all of them in one launch sequence, in the (now free)
-  // augmented-matrix region; Gauss-Jordan with partial pivoting above its register capacity
-  // (N > 2048)
-  {
-    double* lu_out[BO_MAX_OBJ];
-    const double* lu_km[BO_MAX_OBJ];
-    int n_lu = 0;
-    for (int o = 0; o < n_obj; ++o)
-      if (fail[o]) { lu_out[n_lu] = out + (long long)o * n * n; lu_km[n_lu] = km + (long long)o * ld * ld; ++n_lu; }
-    if (n_lu > 0 && n <= bo_lu_max_n() && geo_bytes(g) >= bo_lu_workspace_size(n, n_lu)) {
-      const int st2 = bo_lu_inverse(lu_out, lu_km, n_lu, ld, n, jitter, A, geo_bytes(g), s);
-      __atomic_fetch_add(&g_inv_paths[1], n_lu, __ATOMIC_RELAXED);
-      if (st2 != BO_OK) return st2;
-      for (int o = 0; o < n_obj; ++o) fail[o] = 0;
-    }
-  }
+  st = inv_lu_batch(out, km, ld, n_obj, n, jitter, j.A, L.bufA - L.A, fail, s);
+  if (st != BO_OK) return st;
   for (int o = 0; o < n_obj; ++o) path[o] = fail[o] ? 2 : path[o];
   if (path_out)
     for (int o = 0; o < n_obj; ++o) path_out[o] = path[o];
   for (int o = 0; o < n_obj; ++o) {
     if (!fail[o]) continue;
     __atomic_fetch_add(&g_inv_paths[2], 1, __ATOMIC_RELAXED);
-    int* gstat = status + BO_MAX_OBJ + 1;
-    BO_CHECK_HIP(hipMemsetAsync(gstat, 0, sizeof(int), s));
-    const long long total = (long long)n * n;
-    hipLaunchKernelGGL(jitter_copy_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       bufA, km, (long long)ld, (int)n, o, jitter);
-    BO_CHECK_HIP(hipGetLastError());
-    const int tiles = (int)((n + GJ_TILE - 1) / GJ_TILE);
-    const size_t col_lds = (size_t)n * sizeof(double);
-    if (col_lds > 64 * 1024)
-      BO_CHECK_HIP(hipFuncSetAttribute((const void*)gj_step_kernel,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)col_lds));
-    double* src = bufA;
-    double* dst = bufB;
-    for (int k = 0; k < n; ++k) {
-      hipLaunchKernelGGL(gj_step_kernel, dim3(tiles, tiles), dim3(256), col_lds, s, dst, src, (int)n,
-                         k, piv, gstat);
-      double* t = src; src = dst; dst = t;
-    }
-    BO_CHECK_HIP(hipGetLastError());
-    std::vector<int> hpiv((size_t)n);
-    int gs = 0;
-    BO_CHECK_HIP(hipMemcpyAsync(hpiv.data(), piv, sizeof(int) * n, hipMemcpyDeviceToHost, s));
-    BO_CHECK_HIP(hipMemcpyAsync(&gs, gstat, sizeof(int), hipMemcpyDeviceToHost, s));
-    BO_CHECK_HIP(hipStreamSynchronize(s));
-    if (gs) return BO_ERR_SINGULAR;
-    // column permutation: apply swaps (k, piv[k]) for k = n-1 .. 0 to the identity ordering
-    std::vector<int> hperm((size_t)n);
-    for (int j = 0; j < n; ++j) hperm[j] = j;
-    for (long long k = n - 1; k >= 0; --k) {
-      const int pk = hpiv[k];
-      const int t = hperm[k]; hperm[k] = hperm[pk]; hperm[pk] = t;
-    }
-    BO_CHECK_HIP(hipMemcpyAsync(perm, hperm.data(), sizeof(int) * n, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(gather_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s,
-                       out + (long long)o * n * n, src, perm, (int)n);
-    BO_CHECK_HIP(hipGetLastError());
-    BO_CHECK_HIP(hipStreamSynchronize(s));
+    st = gj_inverse(out, km, ld, n, o, jitter, (double*)(w + L.bufA), (double*)(w + L.bufB), (int*)(w + L.piv),
+                    (int*)(w + L.perm), j.status + kInvStatGJ, s);
+    if (st != BO_OK) return st;
   }
   return BO_OK;
 }
@@ -1781,9 +1764,7 @@ int bo_fit_path_counts(int64_t* counts) {
 
 size_t bo_compute_mll_workspace_size(int32_t n_obj, int64_t n) {
   if (n_obj < 1 || n < 1) return 0;
-  const Geo g = make_geo((int)n, n_obj, false);
-  return geo_bytes(g) + a256((size_t)n_obj * part_len(g) * sizeof(double) + BO_MAX_OBJ * sizeof(int)) + 512 +
-         flag_bytes(g);
+  return mll_layout(make_geo((int)n, n_obj, false)).total;
 }
 
 int bo_compute_mll_each(double* mll_obj, const double* x, int32_t dim, const double* y, int64_t ld_y,
@@ -1803,56 +1784,51 @@ int bo_compute_mll_each_jitter(double* mll_obj, const double* x, int32_t dim, co
   if (n > (1 << 16)) return BO_ERR_UNSUPPORTED;
   if (!ws || ws_bytes < bo_compute_mll_workspace_size(n_obj, n)) return BO_ERR_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
-  const Geo g = make_geo((int)n, n_obj, false);
-  double* A = (double*)ws;
-  // the per-step partials and the status flags go straight to pinned host memory (plain device
-  // stores; visible after the stream synchronisation): no status memset and no read-back copy
-  // per call -- two launches and their boundaries less per Powell evaluation
-  const size_t bytes = (size_t)n_obj * part_len(g) * sizeof(double) + sizeof(int) * (n_obj + 2);
-  double* h = (double*)pinned(bytes);
+  FitJob j;
+  memset(&j, 0, sizeof(j));
+  j.g = make_geo((int)n, n_obj, false);
+  const Geo& g = j.g;
+  const MllLayout L = mll_layout(g);
+  const MllHost H = mll_host(g);
+  char* h = (char*)pinned(H.total);
   if (!h) return BO_ERR_HIP;
-  double* part = h;
-  int* status = (int*)(part + (size_t)n_obj * part_len(g));
-  int* habort = status + n_obj;
-  int* hdone = habort + 1;
-  int* flags = (int*)((char*)ws + geo_bytes(g) +
-                      a256((size_t)n_obj * part_len(g) * sizeof(double) + BO_MAX_OBJ * sizeof(int)) + 512);
-  FitParams p;
-  memset(&p, 0, sizeof(p));
+  j.A = (double*)((char*)ws + L.A);
+  j.km = km;
+  j.ld = ld;
+  j.x = x;
+  j.dim = dim;
+  j.y = y;
+  j.ld_y = ld_y;
   for (int o = 0; o < n_obj; ++o) {
-    p.pv[o] = pv[o];
-    p.pm[o] = pm[o];
-    p.ls2[o] = ls[o] * ls[o];
+    j.p.pv[o] = pv[o];
+    j.p.pm[o] = pm[o];
+    j.p.ls2[o] = ls[o] * ls[o];
   }
-  p.jitter = jitter;
-  bool done = false;
-  if (persist_enabled()) {
-    for (int o = 0; o <= n_obj + 1; ++o) status[o] = 0;          // statuses, abort, done
-    const bool poll = host_poll_enabled();
-    const int st = fit_factor_persist(A, g, km, ld, x, dim, y, ld_y, p, part, status, flags, habort, s,
-                                      poll ? hdone : nullptr);
-    if (st == BO_OK) {
-      if (!poll || !host_poll(hdone)) BO_CHECK_HIP(hipStreamSynchronize(s));
-      done = __atomic_load_n(habort, __ATOMIC_RELAXED) == 0;
-      __atomic_fetch_add(&g_fit_paths[done ? 0 : 2], 1, __ATOMIC_RELAXED);
-    } else if (st != BO_ERR_UNSUPPORTED) {
-      return st;
-    }
-  }
-  if (!done) {
-    __atomic_fetch_add(&g_fit_paths[1], 1, __ATOMIC_RELAXED);
-    for (int o = 0; o < n_obj; ++o) status[o] = 0;
-    const int st = fit_factor(A, g, km, ld, x, dim, y, ld_y, p, part, status, s);
-    if (st != BO_OK) return st;
-    BO_CHECK_HIP(hipStreamSynchronize(s));
-  }
-  const int* hstat = (const int*)(h + (size_t)n_obj * part_len(g));
+  j.p.jitter = jitter;
+  j.part = (double*)(h + H.part);
+  j.status = (int*)(h + H.status);
+  j.flags = (int*)((char*)ws + L.flags);
+  j.habort = (int*)(h + H.abort);
+  j.hdone = host_poll_enabled() ? (int*)(h + H.done) : nullptr;
+  auto clear = [&]() -> int {
+    for (int o = 0; o < n_obj; ++o) j.status[o] = 0;
+    *j.habort = 0;
+    *(int*)(h + H.done) = 0;
+    return BO_OK;
+  };
+  auto wait = [&](bool persistent, bool& aborted) -> int {
+    if (!persistent || !j.hdone || !host_poll(j.hdone)) BO_CHECK_HIP(hipStreamSynchronize(s));
+    aborted = persistent && __atomic_load_n(j.habort, __ATOMIC_RELAXED) != 0;
+    return BO_OK;
+  };
+  const int st = fit_run(j, s, clear, wait);
+  if (st != BO_OK) return st;
   for (int o = 0; o < n_obj; ++o)
-    if (hstat[o]) return BO_ERR_NOT_PD;
+    if (j.status[o]) return BO_ERR_NOT_PD;
   // mll_o = -0.5 yc.alpha - 0.5 log det - 0.5 N log(2 pi) (numba_kernels.py:222-232); yc.alpha =
   // |z|^2 / var(y - pm) (unscaled when the std is 0, :206-207)
   for (int o = 0; o < n_obj; ++o) {
-    const double* q = h + (size_t)o * part_len(g);
+    const double* q = j.part + (size_t)o * part_len(g);
     double ld_sum = 0.0, fit = 0.0;
     for (int k = 0; k < g.nbt; ++k) {
       ld_sum += q[k];

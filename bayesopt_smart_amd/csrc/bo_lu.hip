@@ -1231,28 +1231,28 @@ LuGeo make_lu_geo(int n) {
   g.Na = g.n_p;
   // BO_LU_PANEL=wide: every panel on the 8-wave loop; =small: the 4-wave panel at N <= 512 too
   // (A/B only)
-  static const int small = [] {
-    const char* e = getenv("BO_LU_PANEL");
-    return (e && strcmp(e, "wide") == 0) ? 0 : (e && strcmp(e, "small") == 0) ? 2 :
-           (e && strcmp(e, "small256") == 0) ? 3 : 1;
-  }();
-  g.small_panel = small;
+  const char* e = BO_ENV_ONCE("BO_LU_PANEL");
+  g.small_panel = bo_env_is(e, "wide") ? 0 : bo_env_is(e, "small") ? 2 : bo_env_is(e, "small256") ? 3 : 1;
   return g;
 }
 
-size_t slot_bytes(const LuGeo& g) {
-  return a256((size_t)g.Na * g.n_p * sizeof(double)) + a256((size_t)g.nbs * PREC * sizeof(int)) +
-         a256((size_t)g.n_p * sizeof(int)) + a256((size_t)g.nbs * 512 * sizeof(double));
+// One factorisation's slot of the workspace: byte offsets from the slot's start, one line per
+// array.  The workspace is n_lu slots, then the 256-byte status block.
+struct LuSlot { size_t A, prec, sinv, tinv, total; };
+LuSlot lu_slot(const LuGeo& g) {
+  size_t at = 0;
+  auto take = [&at](size_t bytes) { const size_t off = at; at += a256(bytes); return off; };
+  LuSlot L;
+  L.A = take((size_t)g.Na * g.n_p * sizeof(double));
+  L.prec = take((size_t)g.nbs * PREC * sizeof(int));
+  L.sinv = take((size_t)g.n_p * sizeof(int));
+  L.tinv = take((size_t)g.nbs * 512 * sizeof(double));
+  L.total = at;
+  return L;
 }
 
 // BO_LU_SOLVE=rows: the round-4 solve (interleaved permutations, one row per thread) for A/B
-bool lu_solve_rows() {
-  static const int v = [] {
-    const char* e = getenv("BO_LU_SOLVE");
-    return (e && strcmp(e, "rows") == 0) ? 1 : 0;
-  }();
-  return v != 0;
-}
+bool lu_solve_rows() { return bo_env_is(BO_ENV_ONCE("BO_LU_SOLVE"), "rows"); }
 
 }  // namespace
 
@@ -1261,7 +1261,7 @@ bool lu_solve_rows() {
 // them, BO_ERR_UNSUPPORTED above the register capacity).
 size_t bo_lu_workspace_size(int64_t n, int n_lu) {
   const LuGeo g = make_lu_geo((int)n);
-  return (size_t)n_lu * slot_bytes(g) + 256;
+  return (size_t)n_lu * lu_slot(g).total + 256;
 }
 
 int bo_lu_max_n() { return LT * LRMAX; }
@@ -1273,17 +1273,17 @@ int bo_lu_inverse(double* const* out, const double* const* km, int n_lu, int64_t
   const LuGeo g = make_lu_geo((int)n);
   LuBatch bt;
   memset(&bt, 0, sizeof(bt));
-  char* w = (char*)ws;
+  const LuSlot L = lu_slot(g);
   for (int b = 0; b < n_lu; ++b) {
-    bt.A[b] = (double*)w;
-    bt.prec[b] = (int*)(w + a256((size_t)g.Na * g.n_p * sizeof(double)));
-    bt.sinv[b] = (int*)((char*)bt.prec[b] + a256((size_t)g.nbs * PREC * sizeof(int)));
-    bt.tinv[b] = (double*)((char*)bt.sinv[b] + a256((size_t)g.n_p * sizeof(int)));
+    char* w = (char*)ws + (size_t)b * L.total;
+    bt.A[b] = (double*)(w + L.A);
+    bt.prec[b] = (int*)(w + L.prec);
+    bt.sinv[b] = (int*)(w + L.sinv);
+    bt.tinv[b] = (double*)(w + L.tinv);
     bt.km[b] = km[b];
     bt.out[b] = out[b];
-    w += slot_bytes(g);
   }
-  bt.status = (int*)w;
+  bt.status = (int*)((char*)ws + (size_t)n_lu * L.total);
   BO_CHECK_HIP(hipMemsetAsync(bt.status, 0, sizeof(int) * BO_MAX_OBJ, s));
   const unsigned tiles = (unsigned)((g.n_p + 31) / 32);
   hipLaunchKernelGGL(lu_init_kernel, dim3(tiles, tiles, n_lu), dim3(256), 0, s, bt, g, (long long)ld, jitter);
