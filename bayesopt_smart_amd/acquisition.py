@@ -275,6 +275,140 @@ def hvi_select_indices(acquisition_values, ucb, y_vector, n_evaluations, referen
     return idx[idx >= 0]
 
 
+# ------------------------------------------------- expected hypervolume improvement (EHVI)
+EHVI_FORMS = {"auto": 0, "direct": 1, "table": 2}
+
+
+def ehvi_tables(boxes):
+    """The table form's view of `boxes` (hypervolume_boxes' output, host [n_boxes, 2 n_obj]):
+    (edges, box_idx) -- edges[k] the sorted unique finite bounds of objective k, box_idx int32
+    [n_boxes, 2 n_obj] indices into them, len(edges[k]) standing for +inf (bo_ehvi_tables)."""
+    b = np.ascontiguousarray(np.asarray(boxes, dtype=np.float64))
+    n_obj = b.shape[1] // 2
+    lib = _lib.load()
+    ne = (_C.c_int32 * n_obj)()
+    idx = np.empty((b.shape[0], 2 * n_obj), dtype=np.int32)
+    cap = 64
+    while True:
+        flat = np.empty(cap, dtype=np.float64)
+        st = lib.bo_ehvi_tables(b.ctypes.data, b.shape[0], n_obj, flat.ctypes.data, cap, ne, idx.ctypes.data)
+        if st == _lib.ERR_WORKSPACE and sum(ne) > cap:      # retry with the reported counts
+            cap = sum(ne)
+            continue
+        _lib.check(st, "bo_ehvi_tables")
+        offs = np.concatenate([[0], np.cumsum(list(ne))])
+        return [flat[offs[k]:offs[k + 1]].copy() for k in range(n_obj)], idx
+
+
+class EhviTables:
+    """What the EHVI scan reads besides mu / var, on the device: the boxes of the region `front`
+    does not dominate above `reference_point` (direct form) and their edge tables (table form).
+    Built once per front; `threads` is the table form's workgroup size, 0 when no table fits."""
+
+    def __init__(self, front, reference_point, device=None):
+        self.dev = require_device(device)
+        boxes = hypervolume_boxes(front, reference_point)
+        self.n_obj = boxes.shape[1] // 2
+        self.n_boxes = boxes.shape[0]
+        edges, idx = ehvi_tables(boxes)
+        self.n_edges = (_C.c_int32 * self.n_obj)(*[len(e) for e in edges])
+        self.sum_edges = int(sum(self.n_edges))
+        self.threads = int(_lib.load().bo_ehvi_table_threads(self.sum_edges))
+        self.boxes = torch.as_tensor(boxes, device=self.dev)
+        self.edges = torch.as_tensor(np.concatenate(edges) if edges else np.zeros(0), device=self.dev)
+        self.box_idx = torch.as_tensor(idx, device=self.dev)
+
+
+def expected_hypervolume_improvement(mu, var, front, reference_point, out=None, form="auto", tables=None):
+    """EHVI of every candidate over `front` above `reference_point` (maximisation; independent
+    objectives Y_k ~ N(mu[k], |var[k]|), the predict's mu_objectives / variance_objectives in
+    objective units, [n_obj, M], numpy or HIP tensors):
+    acq = sum_b prod_k [psi_k(l_bk) - psi_k(u_bk)] over hypervolume_boxes' boxes,
+    psi_k(a) = E[(Y_k - a)+] (bo_expected_hypervolume_improvement).  Not in the reference.
+    `form`: "auto", "direct" or "table" (same bits; "table" raises where no table fits the LDS).
+    `tables`: an EhviTables of the front, instead of `front` / `reference_point`.  Returns acq
+    ([M], a device tensor, or numpy for numpy `mu`); written into `out` when given (in place)."""
+    if form not in EHVI_FORMS:
+        raise ValueError(f"unknown form {form!r} (expected 'auto', 'direct' or 'table')")
+    dev = _dev_of(out, mu)
+    m = _Arg(mu, dev)
+    v = _Arg(var, dev)
+    n_obj, n = m.t.shape
+    if m.t.dim() != 2 or v.t.shape != m.t.shape:
+        raise ValueError("mu / var must both be [n_obj, M]")
+    tb = tables if tables is not None else EhviTables(front, reference_point, dev)
+    if tb.n_obj != n_obj:
+        raise ValueError(f"the front has {tb.n_obj} objectives, mu {n_obj}")
+    acq = _Arg(out, dev, write=True) if out is not None else None
+    dst = acq.t if acq is not None else torch.empty(n, dtype=F64, device=dev)
+    if dst.numel() != n:
+        raise ValueError(f"out holds {dst.numel()} values for {n} candidates")
+    nb = tb.n_boxes
+    _lib.check(_lib.load().bo_expected_hypervolume_improvement(
+        dst.data_ptr(), m.ptr, v.ptr, n, n, n_obj,
+        tb.boxes.data_ptr() if nb else None, nb, tb.edges.data_ptr() if nb else None, tb.n_edges,
+        tb.box_idx.data_ptr() if nb else None, EHVI_FORMS[form], stream_handle(dev)),
+        "bo_expected_hypervolume_improvement")
+    if acq is not None:
+        acq.finish()
+        return out
+    return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
+
+
+def _front_of(y_vector, n_evaluations, reference_point):
+    from .pareto import is_pareto_efficient
+    y = y_vector[:n_evaluations]
+    front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
+    return front.cpu().numpy() if isinstance(front, torch.Tensor) else front
+
+
+def update_expected_hypervolume_improvement(acquisition_values, mu_objectives, variance_objectives, y_vector,
+                                            n_evaluations, reference_point):
+    """The acquisition update of the loop (bayesian_optimization.py:195-199) as the EHVI: the front
+    is the Pareto-efficient subset (device filter, pareto.py:12-45) of the evaluated objectives
+    y_vector[:n_evaluations]; in place into `acquisition_values`."""
+    expected_hypervolume_improvement(mu_objectives, variance_objectives,
+                                     _front_of(y_vector, n_evaluations, reference_point), reference_point,
+                                     out=acquisition_values)
+
+
+def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, y_vector, n_evaluations,
+                        reference_point, cands, evaluated_points, batch_size, offset=0, return_record=False,
+                        mask=None):
+    """The EHVI acquisition and its batch selection over one shard, in two launches: the EHVI scan
+    into acquisition_values (device, [count]: the candidates [offset, offset + count) of `cands`,
+    over the Pareto front of y_vector[:n_evaluations]), then bo_select_topq_masked over the shard's
+    ExclusionMask (`mask`, updated here with evaluated_points; without one a mask is built for the
+    call).  batch_size <= BO_MAX_TOPQ.  Returns the global indices of the shard's best batch_size
+    candidates not equal to an evaluated point (select_next_batch's order, NaN first) -- or,
+    `return_record`, the device record block [2 batch_size] (values, bit-cast int64 indices) for
+    the multi-rank exchange, as hvi_select_indices."""
+    if batch_size > _lib.MAX_TOPQ:
+        raise ValueError(f"ehvi_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
+    dev = _dev_of(acquisition_values, mu_objectives)
+    acq = _Arg(acquisition_values, dev, write=True)
+    n = acq.t.numel()
+    if mask is None:
+        mask = ExclusionMask(cands, offset, n, dev)
+    elif mask.offset != offset or mask.count != n:
+        raise ValueError("ehvi_select_indices: the mask covers another shard")
+    mask.update(evaluated_points)
+    expected_hypervolume_improvement(mu_objectives, variance_objectives,
+                                     _front_of(y_vector, n_evaluations, reference_point), reference_point,
+                                     out=acq.t)
+    rec = torch.empty(2 * batch_size, dtype=F64, device=dev)
+    lib = _lib.load()
+    ws = Workspace.get(lib.bo_select_topq_workspace_size(n, batch_size), dev)
+    _lib.check(lib.bo_select_topq_masked(acq.ptr, n, offset, mask.ptr, batch_size, rec.data_ptr(),
+                                         rec.data_ptr() + 8 * batch_size, ws.data_ptr(), ws.numel(),
+                                         stream_handle(dev)), "bo_select_topq_masked")
+    acq.finish()
+    if return_record:
+        return rec
+    idx = rec[batch_size:].view(torch.int64).cpu().numpy()
+    return idx[idx >= 0]
+
+
 BATCH_STRATEGIES = ("top", "bucb")
 
 

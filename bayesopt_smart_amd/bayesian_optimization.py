@@ -29,8 +29,16 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import (BATCH_STRATEGIES, ExclusionMask, hvi_select_indices, select_batch_bucb, select_indices,
+from .acquisition import (BATCH_STRATEGIES, ExclusionMask, ehvi_select_indices, hvi_select_indices,
+                          select_batch_bucb, select_indices, update_expected_hypervolume_improvement,
                           update_hypervolume_improvement_exact)
+
+ACQUISITIONS = ("sum_ucb", "hvi", "ehvi")
+
+
+def _check_acquisition(acquisition):
+    if acquisition not in ACQUISITIONS:
+        raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi' or 'ehvi')")
 from .config import (DEFAULT_BATCH_SIZE, DEFAULT_BETA, DEFAULT_INITIAL_SAMPLES,
                      DEFAULT_LENGTH_SCALE, DEFAULT_PRIOR_MEAN, DEFAULT_PRIOR_VARIANCE,
                      resolve_float_type)
@@ -207,13 +215,14 @@ class DeviceBackend:
         """Global candidate indices of the next batch (select_next_batch's order, the evaluated
         points excluded).  "sum_ucb" is the reference's acquisition (acquisition.py:89-108, fused
         top-q); "hvi" replaces the acquisition array with the exact hypervolume improvement of the
-        UCB vectors over the Pareto front of `y_evaluated` above `reference_point`.
+        UCB vectors over the Pareto front of `y_evaluated` above `reference_point`; "ehvi" with the
+        expected hypervolume improvement of the posterior (mu_objectives, variance_objectives) over
+        that front (acquisition.ehvi_select_indices; not in the reference).
         batch_strategy "top" is the reference's batch (the batch_size best values of one
         acquisition array); "bucb" (not in the reference) takes every pick after the first from the
         UCB recomputed with the variance conditioned on the earlier picks
         (acquisition.select_batch_bucb), over this process's shard."""
-        if acquisition not in ("sum_ucb", "hvi"):
-            raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb' or 'hvi')")
+        _check_acquisition(acquisition)
         _check_batch_strategy(batch_strategy, acquisition, batch_size, self.group)
         xd, yd, kinv = fitted
         out = self._outputs()
@@ -237,17 +246,23 @@ class DeviceBackend:
         predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
                         outputs=tuple(out), topq=0, offset=self.offset, count=self.count, out=out,
                         device=self.dev, mode=self.mode, float_type=self.float_type)
-        if acquisition == "hvi" and batch_size <= _lib.MAX_TOPQ:
-            # the exact HVI and its top-q with exclusion in one device pass over this shard, then
-            # the fused path's exchange
+        if acquisition in ("hvi", "ehvi") and batch_size <= _lib.MAX_TOPQ:
+            # the exact HVI and its top-q with exclusion in one device pass over this shard (the
+            # EHVI: its scan, then the masked top-q), then the fused path's exchange
             # the shard's exclusion mask persists across iterations: only the new batch's rows
             # are added to it (ExclusionMask)
             if self._excl_mask is None:
                 self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
-            rec = hvi_select_indices(self.bufs.acquisition_values, self.bufs.ucb, y_evaluated,
-                                     len(y_evaluated), reference_point, prior_mean, prior_variance,
-                                     self.cands, evaluated, batch_size, offset=self.offset,
-                                     return_record=True, mask=self._excl_mask)
+            if acquisition == "hvi":
+                rec = hvi_select_indices(self.bufs.acquisition_values, self.bufs.ucb, y_evaluated,
+                                         len(y_evaluated), reference_point, prior_mean, prior_variance,
+                                         self.cands, evaluated, batch_size, offset=self.offset,
+                                         return_record=True, mask=self._excl_mask)
+            else:
+                rec = ehvi_select_indices(self.bufs.acquisition_values, self.bufs.mu_objectives,
+                                          self.bufs.variance_objectives, y_evaluated, len(y_evaluated),
+                                          reference_point, self.cands, evaluated, batch_size,
+                                          offset=self.offset, return_record=True, mask=self._excl_mask)
             from .distributed import collectives_on, exchange_topq_rec
             if not collectives_on(self.group):
                 idx = rec[batch_size:].view(torch.int64).cpu().numpy()
@@ -257,6 +272,10 @@ class DeviceBackend:
             update_hypervolume_improvement_exact(self.bufs.acquisition_values, self.bufs.ucb, y_evaluated,
                                                  len(y_evaluated), reference_point, prior_mean,
                                                  prior_variance)
+        if acquisition == "ehvi":
+            update_expected_hypervolume_improvement(self.bufs.acquisition_values, self.bufs.mu_objectives,
+                                                    self.bufs.variance_objectives, y_evaluated,
+                                                    len(y_evaluated), reference_point)
         # batches above BO_MAX_TOPQ: rounds of the standalone device selection (over the gathered
         # array when sharded)
         from .distributed import collectives_on
@@ -303,7 +322,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     registered on rank 0 only keeps every rank's collectives matched.
     """
     del k_star, n_objectives, bounds  # unused, as in the reference (reference_point too, unless
-    #                                   acquisition="hvi", the exact hypervolume improvement)
+    #                                   acquisition="hvi" / "ehvi", the exact / expected hypervolume improvement)
     n_obj = len(prior_mean)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, getattr(backend, "group", group))
     if backend is None:
@@ -426,6 +445,9 @@ def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", 
     if acquisition == "hvi" and n_obj > 4:
         raise ValueError(f"acquisition='hvi' supports at most 4 objectives (got {n_obj}): the exact "
                          "hypervolume improvement's box decomposition is limited to n_obj <= 4")
+    if acquisition == "ehvi" and n_obj > 4:
+        raise ValueError(f"acquisition='ehvi' supports at most 4 objectives (got {n_obj}): the expected "
+                         "hypervolume improvement's box decomposition is limited to n_obj <= 4")
     if not 1 <= dim <= _lib.MAX_DIM:
         raise ValueError(f"the input dimension must be in [1, {_lib.MAX_DIM}] (got {dim})")
     if batch_size < 1:
@@ -445,8 +467,9 @@ class BayesianOptimization:
 
     Extra kwargs (not in the reference): ``input_space`` (explicit [M, d] candidates, e.g.
     a Sobol set, or a CandidateSet such as CandidateSet.sobol_set(...), instead of the integer
-    grid), ``device``, ``acquisition`` ("sum_ucb", the reference's default, or "hvi": exact
-    hypervolume improvement of the UCB vectors over the evaluated Pareto front),
+    grid), ``device``, ``acquisition`` ("sum_ucb", the reference's default; "hvi": exact
+    hypervolume improvement of the UCB vectors over the evaluated Pareto front; or "ehvi": the
+    expected hypervolume improvement of the posterior over that front, objectives independent),
     ``reference_point`` (the HVI reference point; the reference fixes it at zeros and never uses
     it, bayesian_optimization.py:425), ``group`` (the torch.distributed process group of a
     multi-GPU run; default: the world when initialised), ``float_type`` (np.float64, the default
@@ -497,8 +520,7 @@ class BayesianOptimization:
         self._input_space = None
         self.total_samples = self.initial_samples + self.n_iterations * self.batch_size
         self.acquisition = kwargs.get("acquisition", "sum_ucb")
-        if self.acquisition not in ("sum_ucb", "hvi"):
-            raise ValueError(f"unknown acquisition {self.acquisition!r} (expected 'sum_ucb' or 'hvi')")
+        _check_acquisition(self.acquisition)
         self.batch_strategy = kwargs.get("batch_strategy", "top")
         _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
                       self.batch_strategy, self.group)

@@ -1,0 +1,277 @@
+// Expected hypervolume improvement (EHVI) of each candidate's posterior over the Pareto front of
+// the evaluated points (maximisation, reference point r).  NOT in the reference, which has no
+// EHVI: parity is unpinned by it (tests/ehvi_ref.py is the independent statement).
+//
+// With independent objectives Y_k ~ N(mu_k, sigma_k^2) (the reference's model: one GP per
+// objective) and the disjoint boxes [l_b, u_b) of bo_hvi_boxes, the expectation of the box sum
+// hvi_exact_kernel evaluates (bo_hvi.hip) has the closed form
+//
+//   EHVI = sum_b prod_k [ psi_k(l_bk) - psi_k(u_bk) ]
+//   psi_k(a) = E[(Y_k - a)+] = sigma_k (phi(z) + z Phi(z)),  z = (mu_k - a) / sigma_k,  psi_k(+inf) = 0
+//
+// because E[max(0, min(Y, u) - l)] = psi(l) - psi(u) and the objectives are independent.
+//
+// Two forms, one psi, one box order, the same arithmetic per box (results equal bit for bit):
+//   direct: psi at every bound of every box (2 m per box, the +inf bounds skipped), boxes read at
+//           wave-uniform addresses;
+//   table:  the boxes' bounds are copies of few edge coordinates (bo_ehvi_tables: per axis the
+//           sorted unique finite bounds, E_k of them), so a thread evaluates psi_k at every edge
+//           once into its own column of an LDS table [edge][thread] and the box sum is then
+//           multiplies and adds over that column.
+//
+// psi is evaluated as  max(d, 0) + sigma h(|z|),  d = mu - a,  h(t) = phi(t) - t Phi(-t)
+//                      = exp(-t^2/2) (1/sqrt(2 pi) - t erfcx(t / sqrt 2) / 2):
+// phi + z Phi itself cancels for z < 0, and the linear part max(d, 0) is exact here.
+
+#include "bo_common.h"
+
+#include <math.h>
+#include <string.h>
+
+#include <algorithm>
+#include <cmath>
+#include <vector>
+
+// both kernels must round alike: no contraction but the fma written out below
+#pragma clang fp contract(off)
+
+namespace {
+
+constexpr int kEhviLdsBytes = 160 * 1024;      // LDS of a CU: one workgroup may hold all of it
+constexpr int kEhviAuto2dEdges = 40;           // auto, 2 objectives: two 256-thread tables per CU
+
+struct EhviArgs {
+  double* acq;
+  const double* mu;
+  const double* var;
+  long long ld, n;
+  const double* boxes;     // direct: [n_boxes][2 m] (bo_hvi_boxes)
+  const double* edges;     // table: the axes' edges, concatenated
+  const int* box_idx;      // table: [n_boxes][2 m] indices into the axis' edges; E_k = +inf
+  long long n_boxes;
+  int n_edges[4], edge_off[4];
+};
+
+// sigma h(t), t = |d| rs with rs = 1 / sigma.  sigma = 0 gives t = inf (or NaN at d = 0) and the
+// limit 0; h underflows to 0 well before t = 40.
+__device__ __forceinline__ double ehvi_psi(double d, double sigma, double rs) {
+  const double t = fabs(d * rs);
+  double h = 0.0;
+  if (t < 40.0) {
+    const double e = exp(-0.5 * (t * t));
+    h = e * (0.3989422804014327 - (0.5 * t) * erfcx(t * 0.7071067811865476));
+  }
+  return __builtin_fma(sigma, h, fmax(d, 0.0));
+}
+
+template <int M>
+__device__ __forceinline__ bool ehvi_load(const EhviArgs& a, long long i, bool valid, double* mu, double* sg,
+                                          double* rs) {
+  bool nan = false;
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    mu[k] = valid ? __builtin_nontemporal_load(a.mu + (long long)k * a.ld + i) : 0.0;
+    const double v = valid ? __builtin_nontemporal_load(a.var + (long long)k * a.ld + i) : 1.0;
+    nan = nan || (mu[k] != mu[k]) || (v != v);
+    sg[k] = sqrt(fabs(v));
+    rs[k] = 1.0 / sg[k];
+  }
+  return nan;
+}
+
+// One thread per candidate, one candidate per thread: no store precedes the loads of the boxes,
+// which are then scalar loads at a wave-uniform address, in order.
+template <int M>
+__global__ __launch_bounds__(256) void ehvi_direct_kernel(const EhviArgs a) {
+  const double inf = __builtin_inf();
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  const bool valid = i < a.n;
+  double mu[M], sg[M], rs[M];
+  const bool nan = ehvi_load<M>(a, i, valid, mu, sg, rs);
+  double h = 0.0;
+  const double* b = a.boxes;
+  for (long long t = 0; t < a.n_boxes; ++t, b += 2 * M) {
+    double v = 1.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const double pl = ehvi_psi(mu[k] - b[k], sg[k], rs[k]);
+      const double pu = b[M + k] < inf ? ehvi_psi(mu[k] - b[M + k], sg[k], rs[k]) : 0.0;
+      if (k < M - 1) v *= pl - pu;
+      else h = __builtin_fma(v, pl - pu, h);
+    }
+  }
+  if (valid) bo_out_store(a.acq + i, nan ? __builtin_nan("") : h);
+}
+
+// One thread per candidate, one candidate per thread; T threads per workgroup; the table
+// [sum E][T] in dynamic LDS.  A thread reads only the column it wrote, so there is no barrier.
+template <int M, int T>
+__global__ __launch_bounds__(T) void ehvi_table_kernel(const EhviArgs a) {
+  extern __shared__ double ehvi_tab[];
+  double* col = ehvi_tab + threadIdx.x;
+  const long long i = (long long)blockIdx.x * T + threadIdx.x;
+  const bool valid = i < a.n;
+  double mu[M], sg[M], rs[M];
+  const bool nan = ehvi_load<M>(a, i, valid, mu, sg, rs);
+#pragma unroll
+  for (int k = 0; k < M; ++k) {
+    const double* e = a.edges + a.edge_off[k];
+    double* c = col + a.edge_off[k] * T;
+#pragma unroll 2
+    for (int j = 0; j < a.n_edges[k]; ++j) c[j * T] = ehvi_psi(mu[k] - e[j], sg[k], rs[k]);
+  }
+  double h = 0.0;
+  const int* b = a.box_idx;
+  for (long long t = 0; t < a.n_boxes; ++t, b += 2 * M) {
+    double v = 1.0;
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+      const double pl = col[(a.edge_off[k] + b[k]) * T];
+      const double pu = b[M + k] < a.n_edges[k] ? col[(a.edge_off[k] + b[M + k]) * T] : 0.0;
+      if (k < M - 1) v *= pl - pu;
+      else h = __builtin_fma(v, pl - pu, h);
+    }
+  }
+  if (valid) bo_out_store(a.acq + i, nan ? __builtin_nan("") : h);
+}
+
+long long ehvi_blocks(long long n, int threads) { return (n + threads - 1) / threads; }
+
+int launch_direct(const EhviArgs& a, int m, hipStream_t s) {
+  const dim3 g((unsigned)ehvi_blocks(a.n, 256));
+  switch (m) {
+    case 1: hipLaunchKernelGGL(ehvi_direct_kernel<1>, g, dim3(256), 0, s, a); break;
+    case 2: hipLaunchKernelGGL(ehvi_direct_kernel<2>, g, dim3(256), 0, s, a); break;
+    case 3: hipLaunchKernelGGL(ehvi_direct_kernel<3>, g, dim3(256), 0, s, a); break;
+    case 4: hipLaunchKernelGGL(ehvi_direct_kernel<4>, g, dim3(256), 0, s, a); break;
+    default: return BO_ERR_UNSUPPORTED;
+  }
+  BO_CHECK_HIP(hipGetLastError());
+  return BO_OK;
+}
+
+template <int M, int T>
+int launch_table_mt(const EhviArgs& a, int sum_e, hipStream_t s) {
+  const size_t lds = (size_t)sum_e * T * sizeof(double);
+  if (lds > 64 * 1024)
+    BO_CHECK_HIP(hipFuncSetAttribute((const void*)ehvi_table_kernel<M, T>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  hipLaunchKernelGGL((ehvi_table_kernel<M, T>), dim3((unsigned)ehvi_blocks(a.n, T)), dim3(T), lds, s, a);
+  BO_CHECK_HIP(hipGetLastError());
+  return BO_OK;
+}
+
+template <int M>
+int launch_table_m(const EhviArgs& a, int sum_e, int threads, hipStream_t s) {
+  switch (threads) {
+    case 256: return launch_table_mt<M, 256>(a, sum_e, s);
+    case 128: return launch_table_mt<M, 128>(a, sum_e, s);
+    case 64: return launch_table_mt<M, 64>(a, sum_e, s);
+    default: return BO_ERR_UNSUPPORTED;
+  }
+}
+
+int launch_table(const EhviArgs& a, int m, int sum_e, int threads, hipStream_t s) {
+  switch (m) {
+    case 1: return launch_table_m<1>(a, sum_e, threads, s);
+    case 2: return launch_table_m<2>(a, sum_e, threads, s);
+    case 3: return launch_table_m<3>(a, sum_e, threads, s);
+    case 4: return launch_table_m<4>(a, sum_e, threads, s);
+    default: return BO_ERR_UNSUPPORTED;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+// The table form's admission rule (include/bo_amd.h states it; tests/ehvi_ref.py mirrors it).
+int bo_ehvi_table_threads(int64_t sum_edges) {
+  if (sum_edges < 0) return 0;
+  for (int t = 256; t >= 64; t /= 2)
+    if (sum_edges <= kEhviLdsBytes / (t * (int)sizeof(double))) return t;
+  return 0;
+}
+
+int bo_ehvi_tables(const double* boxes, int64_t n_boxes, int32_t n_obj, double* edges, int64_t edge_capacity,
+                   int32_t* n_edges, int32_t* box_idx) {
+  if (!n_edges || n_obj < 1 || n_obj > 4 || n_boxes < 0 || n_boxes > ((int64_t)1 << 26) ||
+      (n_boxes > 0 && !boxes) || edge_capacity < 0 || (edge_capacity > 0 && !edges))
+    return BO_ERR_ARG;
+  const int m = n_obj;
+  // a lower bound is finite, an upper bound finite or +inf, and neither is NaN
+  for (int64_t b = 0; b < n_boxes; ++b)
+    for (int k = 0; k < m; ++k) {
+      const double lo = boxes[b * 2 * m + k], hi = boxes[b * 2 * m + m + k];
+      if (!std::isfinite(lo) || hi != hi || hi == -__builtin_inf()) return BO_ERR_ARG;
+    }
+  std::vector<std::vector<double>> e(m);
+  int64_t total = 0;
+  for (int k = 0; k < m; ++k) {
+    for (int64_t b = 0; b < n_boxes; ++b) {
+      e[k].push_back(boxes[b * 2 * m + k]);
+      if (std::isfinite(boxes[b * 2 * m + m + k])) e[k].push_back(boxes[b * 2 * m + m + k]);
+    }
+    std::sort(e[k].begin(), e[k].end());
+    e[k].erase(std::unique(e[k].begin(), e[k].end()), e[k].end());
+    n_edges[k] = (int32_t)e[k].size();
+    total += (int64_t)e[k].size();
+  }
+  if (total > edge_capacity || (n_boxes > 0 && !box_idx)) return BO_ERR_WORKSPACE;
+  int64_t off = 0;
+  for (int k = 0; k < m; ++k) {
+    std::copy(e[k].begin(), e[k].end(), edges + off);
+    off += (int64_t)e[k].size();
+    for (int64_t b = 0; b < n_boxes; ++b)
+      for (int side = 0; side < 2; ++side) {
+        const double v = boxes[b * 2 * m + side * m + k];
+        box_idx[b * 2 * m + side * m + k] =
+            std::isfinite(v) ? (int32_t)(std::lower_bound(e[k].begin(), e[k].end(), v) - e[k].begin())
+                             : n_edges[k];
+      }
+  }
+  return BO_OK;
+}
+
+int bo_expected_hypervolume_improvement(double* acq, const double* mu, const double* var, int64_t ld, int64_t n,
+                                        int32_t n_obj, const double* boxes, int64_t n_boxes, const double* edges,
+                                        const int32_t* n_edges, const int32_t* box_idx, int32_t form, void* stream) {
+  if (!acq || !mu || !var || n < 0 || ld < n || n_obj < 1 || n_obj > 4 || n_boxes < 0 || form < 0 || form > 2)
+    return BO_ERR_ARG;
+  if (n > ((int64_t)1 << 36)) return BO_ERR_UNSUPPORTED;     // one thread per candidate: the grid's limit
+  const bool have_tables = n_edges && (n_boxes == 0 || (edges && box_idx));
+  const bool have_boxes = n_boxes == 0 || boxes;
+  if ((form == 1 && !have_boxes) || (form == 2 && !have_tables) || (form == 0 && !have_boxes && !have_tables))
+    return BO_ERR_ARG;
+  EhviArgs a;
+  memset(&a, 0, sizeof(a));
+  int64_t sum_e = 0;
+  if (have_tables)
+    for (int k = 0; k < n_obj; ++k) {
+      if (n_edges[k] < 0 || (n_boxes > 0 && n_edges[k] < 1)) return BO_ERR_ARG;
+      a.n_edges[k] = n_edges[k];
+      a.edge_off[k] = (int)sum_e;
+      sum_e += n_edges[k];
+      if (sum_e > ((int64_t)1 << 20)) return BO_ERR_UNSUPPORTED;
+    }
+  const int threads = have_tables ? bo_ehvi_table_threads(sum_e) : 0;
+  if (form == 2 && threads == 0) return BO_ERR_UNSUPPORTED;
+  // auto: the rule of include/bo_amd.h (measured: profiles/ehvi_c3.jsonl)
+  const bool table = form == 2 || (form == 0 && threads != 0 && n_boxes > 0 &&
+                                   (!have_boxes || n_obj >= 3 || (n_obj == 2 && sum_e <= kEhviAuto2dEdges)));
+  if (!table && !have_boxes) return BO_ERR_UNSUPPORTED;      // auto, tables only, and they do not fit
+  if (n == 0) return BO_OK;
+  a.acq = acq;
+  a.mu = mu;
+  a.var = var;
+  a.ld = ld;
+  a.n = n;
+  a.boxes = boxes;
+  a.edges = edges;
+  a.box_idx = box_idx;
+  a.n_boxes = n_boxes;
+  return table ? launch_table(a, n_obj, (int)sum_e, threads, (hipStream_t)stream)
+               : launch_direct(a, n_obj, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -354,6 +354,56 @@ int bo_hypervolume_improvement_exact(double* acq, const double* ucb, int64_t ld,
                                      int32_t n_obj, const double* shift, const double* scale,
                                      const double* boxes, int64_t n_boxes, void* stream);
 
+/* Expected hypervolume improvement (EHVI; opt-in acquisition "ehvi").  NOT in the reference,
+ * which has no EHVI: parity is unpinned by it.  With independent objectives
+ * Y_k ~ N(mu_k, sigma_k^2), sigma_k = sqrt(|var_k|) (the UCB's convention), and the disjoint boxes
+ * [l_b, u_b) of bo_hvi_boxes, the expectation of the box sum bo_hypervolume_improvement_exact
+ * evaluates is
+ *   EHVI = sum_b prod_k [ psi_k(l_bk) - psi_k(u_bk) ],
+ *   psi_k(a) = E[(Y_k - a)+] = sigma_k (phi(z) + z Phi(z)), z = (mu_k - a) / sigma_k, psi_k(+inf) = 0.
+ *
+ * bo_ehvi_tables (HOST, synchronous, no device memory): the boxes' bounds are copies of few
+ * coordinates (the reference point, the front's values, the columns' floors).  From `boxes`
+ * (host, bo_hvi_boxes' output [n_boxes][2 n_obj]) it writes, per objective k, the sorted unique
+ * finite bounds -- n_edges[k] = E_k of them, concatenated in `edges` (host, objective 0 first) --
+ * and per box 2 n_obj int32 indices into its axis' edges (box_idx, host [n_boxes][2 n_obj], laid
+ * out as the box: lower[n_obj], upper[n_obj]); index E_k stands for +inf.  The lookup is exact.
+ * n_edges (host [n_obj]) is always written; returns BO_ERR_WORKSPACE, with nothing else written,
+ * when sum_k E_k exceeds `edge_capacity` (doubles in `edges`).  An empty front (one box) gives
+ * E_k = 1.  n_obj <= 4.
+ *
+ * bo_expected_hypervolume_improvement: acq[i] = EHVI of candidate i, from mu / var (device
+ * [n_obj][ld], the predict's mu_objectives / variance_objectives in objective units).  NaN in any
+ * mu_k or var_k gives NaN (selected first, as for the exact HVI); sigma = 0 gives the limit
+ * psi(a) = max(mu - a, 0); n_boxes = 0 gives 0.  Asynchronous on `stream`, capturable in a HIP
+ * graph, deterministic (fixed box order, no atomics).  `form`:
+ *   1  direct: psi at every finite bound of every box; needs `boxes` (device copy of
+ *      bo_hvi_boxes' output) only.
+ *   2  table: one thread per candidate evaluates psi_k at every edge of every axis once into its
+ *      column of an LDS table [edge][thread] and then walks the boxes' index tuples; needs
+ *      `edges` (device), `n_edges` (HOST [n_obj]) and `box_idx` (device).  ADMISSION RULE: the
+ *      table holds S = sum_k E_k doubles per thread; the workgroup is the largest
+ *      T in {256, 128, 64} with 8 S T <= 163840 bytes (the 160 KiB LDS of a CU), i.e. T = 256 for
+ *      S <= 80, 128 for S <= 160, 64 for S <= 320 -- bo_ehvi_table_threads returns T, or 0 when
+ *      no table fits, and then form 2 returns BO_ERR_UNSUPPORTED.
+ *   0  auto: the table form where it is admitted and was measured not slower than the direct
+ *      form, else the direct form; pointers of the form not taken may be NULL.  AUTO'S RULE
+ *      (profiles/ehvi_c3.jsonl, 2^20 candidates): with 3 or 4 objectives
+ *      the table form wherever it is admitted (1.16x to 9.6x the direct form's speed at S = 36 ..
+ *      303); with 2 objectives for S <= 40 only, where two 256-thread tables fit a CU (1.26x ..
+ *      1.37x at S = 18, 34, 40; 0.88x and 0.92x at S = 42 and 66, where one table leaves a CU
+ *      with one wave per SIMD); with 1 objective (one box, one psi) the direct form.
+ * Both forms use one psi and one box order and give the same bits.  bo_ehvi_tables also returns
+ * BO_ERR_WORKSPACE when box_idx is NULL with n_boxes > 0 (a query of the counts). */
+int bo_ehvi_tables(const double* boxes, int64_t n_boxes, int32_t n_obj, double* edges,
+                   int64_t edge_capacity, int32_t* n_edges, int32_t* box_idx);
+int bo_ehvi_table_threads(int64_t sum_edges);
+int bo_expected_hypervolume_improvement(double* acq, const double* mu, const double* var,
+                                        int64_t ld, int64_t n, int32_t n_obj, const double* boxes,
+                                        int64_t n_boxes, const double* edges,
+                                        const int32_t* n_edges, const int32_t* box_idx,
+                                        int32_t form, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * GP fit on device.
  * ---------------------------------------------------------------------------------- */
