@@ -43,7 +43,11 @@ constexpr int kClassLists = kConvClasses * kConvShards;   // the class lists of 
 static_assert(kClassLists % 64 == 0 && kClassLists <= 2 * 64 * kConvAccWaves &&
               (kConvShards & (kConvShards - 1)) == 0 && kConvShards <= 16 && kConvShards <= kConvCountStride,
               "conv_acc_kernel's scan and lookup of the class lists");
-constexpr int kConvPF = 3;               // A-operand prefetch depth of the contraction (k-blocks)
+#ifndef BO_CONV_PF
+#define BO_CONV_PF 3                      // BO_BUILD_VARIANT=DEF_CONV_PF=6: the A/B of DESIGN.md §9.6 item 6
+#endif
+constexpr int kConvPF = BO_CONV_PF;      // A-operand prefetch depth of the contraction (k-blocks)
+constexpr int kContractWaves = 8;        // most waves of a contraction workgroup: two per SIMD, 256 VGPRs each
 constexpr size_t kConvLdsBytes = 160 * 1024;
 // a pair whose |w_nm| is below kPairDrop pv for every objective is left out of the list: at most
 // N (N + 1) / 2 of them, so q / pv loses less than 1e-24 for N <= 4096
@@ -69,10 +73,13 @@ struct AccLds {          // doubles: tabE[2][2R]; then ints, to a whole double: 
 };
 struct ContractLds {     // doubles: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] (ints, one double); then ints: cn[NP]
   int HB, tabH, hband, cn;
-  size_t bytes;
-  __host__ __device__ ContractLds(int C, int Cpad, int LT, int NP)
+  size_t bytes;          // the tables, or the `lists` top-q entries that the waves of a workgroup merge from offset 0
+                         // once the tables are done with (more than the tables only on a grid of a few columns)
+  __host__ __device__ ContractLds(int C, int Cpad, int LT, int NP, int lists = 0)
       : HB(Cpad + LT / 2), tabH(2 * HB), hband(tabH + Cpad + C - 1), cn(hband + 1),
-        bytes((size_t)cn * sizeof(double) + (size_t)NP * sizeof(int)) {}
+        bytes((size_t)cn * sizeof(double) + (size_t)NP * sizeof(int)) {
+    if (bytes < (size_t)lists * sizeof(TopEntry)) bytes = (size_t)lists * sizeof(TopEntry);
+  }
 };
 
 // ---------------------------------------------------------------------------------------
@@ -431,9 +438,11 @@ __global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
 }
 
 // ---------------------------------------------------------------------------------------
-// Contraction, epilogue and selection.  A wave owns 16 grid rows x 64 columns (4 column blocks:
-// 4 accumulators per GEMM); the 4 waves of a workgroup take consecutive wave tiles (the same rows
-// when the grid has >= 256 columns: their A loads hit the L1).  Per k-block of 16:
+// Contraction, epilogue and selection.  A wave owns 16 grid rows x TW = 16 NB columns (NB column blocks:
+// NB accumulators per GEMM; NB = 4, 2 or 1, the plan's choice: plan_gridconv); the 8 or 4 waves of a
+// workgroup take consecutive wave tiles (the same rows when a grid row has that many tiles: their A loads
+// hit the L1).  Cpad is a multiple of 64 for every NB, and the k-blocks are the absolute 16-row blocks in
+// ascending order: an output element's sum does not depend on NB.  Per k-block of 16:
 //   A: lane (il = l & 15, g = l >> 4) loads X[k0 + 4g + s][i0 + il], s = 0..3 (X = T or Tm, k-major:
 //      16 lanes read 128 contiguous bytes), through a kConvPF-deep register ring;
 //   B: MFMA step s pairs lane group g with k = k0 + 4g + s:
@@ -443,17 +452,28 @@ __global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
 //                in column-bucketed order (`order`), so the points near a tile are consecutive rows.
 // The tables tabB, tabH and hband (ContractLds) are rebuilt when the length scale changes.
 // Bands: table entries below kTabFlush are stored as +0.0, and hband holds the largest |t| of an entry
-// that the same comparison kept (hq for E, hm for H).  A tile of columns j0 .. j0 + 63 runs
-//   variance  the k-blocks that hold a tau of [2 j0 - hq, 2 (j0 + 63) + hq],
-//   mean      the k-blocks that hold a row of cstart[j0 - hm] .. cstart[j0 + 64 + hm] - 1;
+// that the same comparison kept (hq for E, hm for H).  A tile of columns j0 .. j0 + TW - 1 runs
+//   variance  the k-blocks that hold a tau of [2 j0 - hq, 2 (j0 + TW - 1) + hq],
+//   mean      the k-blocks that hold a row of cstart[j0 - hm] .. cstart[j0 + TW + hm] - 1;
 // every other k-block multiplies finite T / Tm by exact zeros, and acc + 0 = acc: the outputs are those
 // of ConvArgs::full (every k-block), bit for bit, and do not depend on what a shard's tiles skipped.
 // The k-blocks ascend for every tile alike; the accumulators are read behind mfma_fence.
+// Selection: a wave keeps a top-q list over its tiles; at the end the waves of a workgroup merge theirs in LDS
+// and the workgroup writes one list, so the grid is bounded by the lists the final merge reads (n_lists), not
+// by the waves.  BO_BUILD_VARIANT=CT_NOOUT / CT_NOSEL / CT_NOTAB / CT_BCONST / CT_ACONST are timing-only builds
+// without the output stores, the selection, the table build, the B operand's LDS reads or the A operand's loads
+// (DESIGN.md §9.6 item 6).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void conv_load_a(const double* __restrict__ X, int ldr, int kb, int g, double (&v)[4]) {
+#ifdef BO_ABL_CT_ACONST
+  // ablation (timing only): no A loads, the operand is one value read once
+#pragma unroll
+  for (int s = 0; s < 4; ++s) v[s] = X[0];
+#else
   const double* p = X + (size_t)(16 * kb + 4 * g) * ldr;
 #pragma unroll
   for (int s = 0; s < 4; ++s) v[s] = p[(size_t)s * ldr];
+#endif
 }
 
 // acc[nb] += X[k-blocks][rows] . B; bgen(kb, bv) fills bv[s][nb], this lane's B values of k-block kb
@@ -461,8 +481,8 @@ __device__ __forceinline__ void conv_load_a(const double* __restrict__ X, int ld
 // that starts at k-block kb_lo passes X advanced by 16 kb_lo rows and a bgen whose base is moved by
 // as much: the first block is then in the pointers, not in a register that lives through the loop
 // (with one, the contraction kernel needed scratch)
-template <class BGen>
-__device__ __forceinline__ void conv_gemm(const double* __restrict__ X, int ldr, int nkb, int g, d4 (&acc)[4],
+template <int NB, class BGen>
+__device__ __forceinline__ void conv_gemm(const double* __restrict__ X, int ldr, int nkb, int g, d4 (&acc)[NB],
                                           BGen&& bgen) {
   double ring[kConvPF][4];
 #pragma unroll
@@ -477,18 +497,20 @@ __device__ __forceinline__ void conv_gemm(const double* __restrict__ X, int ldr,
         for (int s = 0; s < 4; ++s) av[s] = ring[p][s];
         const int nx = kb + kConvPF;
         conv_load_a(X, ldr, nx < nkb ? nx : nkb - 1, g, ring[p]);
-        double bv[4][4];
+        double bv[4][NB];
         bgen(kb, bv);
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-          for (int nb = 0; nb < 4; ++nb) acc[nb] = mfma64(av[s], bv[s][nb], acc[nb]);
+          for (int nb = 0; nb < NB; ++nb) acc[nb] = mfma64(av[s], bv[s][nb], acc[nb]);
       }
     }
   }
 }
 
-__global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a) {
+// NB column blocks per wave tile; 4 or 8 waves per workgroup (blockDim.x, the plan's choice)
+template <int NB>
+__global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(const ConvArgs a) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   extern __shared__ __attribute__((aligned(16))) double sd[];
   const ContractLds L(a.C, a.Cpad, a.LT, a.NP);
@@ -497,22 +519,29 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
   // (the last entry of tabH's region is read by no tile: j - c_n + C - 1 <= Cpad + C - 2)
   int* hband = (int*)(sd + L.hband);                             // the bands of tabB and tabH: hq, hm
   int* cn = (int*)(sd + L.cn);
+  constexpr int TW = 16 * NB;                                    // columns of a wave tile
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int nt = blockDim.x, W = nt >> 6;
   const int g = lane >> 4, jl = lane & 15;
-  const int cb_n = a.Cpad / 64;                                  // wave tiles along a grid row
+  const int cb_n = a.Cpad / TW;                                  // wave tiles along a grid row
   const long long n_wt = (long long)(a.ldr / 16) * cb_n;
   const long long gi_lo = a.cand_offset, gi_hi = a.cand_offset + a.n_cand;
-  for (int t = tid; t < a.NP; t += 256) cn[t] = t < a.n ? a.rc[2 * a.order[t] + 1] : 0;
+#ifndef BO_ABL_CT_NOOUT
+  const bool outs = true;
+#else
+  const bool outs = a.ld_out < 0;                                // ablation (timing only): false, and not known to be
+#endif
+  for (int t = tid; t < a.NP; t += nt) cn[t] = t < a.n ? a.rc[2 * a.order[t] + 1] : 0;
 
   double lv = -__builtin_inf();                                  // the wave's top-q list, lanes 0..q-1
   long long li = -1;
   double tab_nhl = __builtin_nan("");                            // length scale of the tables in LDS
-  for (long long base = (long long)blockIdx.x * 4; base < n_wt; base += (long long)gridDim.x * 4) {
+  for (long long base = (long long)blockIdx.x * W; base < n_wt; base += (long long)gridDim.x * W) {
     const long long wt = base + wave;
     const bool active = wt < n_wt;
     const long long wtc = active ? wt : n_wt - 1;
-    const int i0 = (int)(wtc / cb_n) * 16, j0 = (int)(wtc % cb_n) * 64;
-    double acq[4][4];
+    const int i0 = (int)(wtc / cb_n) * 16, j0 = (int)(wtc % cb_n) * TW;
+    double acq[NB][4];
     for (int o = 0; o < a.n_obj; ++o) {
       // the tables depend on the length scale alone: rebuilt only when it changes (one objective,
       // or equal length scales: built once per workgroup; objectives with different length scales
@@ -524,7 +553,9 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
         // entries below kTabFlush become +0.0 (a NaN entry compares false and stays); the band is
         // the largest |t| that the same comparison kept
         int mq = 0;
-        for (int t = tid; t < 2 * L.HB; t += 256) {
+        int mm = 0;
+#ifndef BO_ABL_CT_NOTAB
+        for (int t = tid; t < 2 * L.HB; t += nt) {
           const int par = t >= L.HB ? 1 : 0, h = t - par * L.HB;
           const int mi = 2 * h + par - (a.LT - 1);
           const double m = (double)mi;
@@ -533,8 +564,7 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
           tabB[t] = flush ? 0.0 : v;
           if (!flush) mq = max(mq, abs(mi));
         }
-        int mm = 0;
-        for (int t = tid; t < a.Cpad + a.C - 1; t += 256) {
+        for (int t = tid; t < a.Cpad + a.C - 1; t += nt) {
           const int mi = t - (a.C - 1);
           const double m = (double)mi;
           const double v = exp(nhl * (m * m));
@@ -542,6 +572,11 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
           tabH[t] = flush ? 0.0 : v;
           if (!flush) mm = max(mm, abs(mi));
         }
+#else
+        // ablation (timing only): the tables stay as they are; the bands from the flush threshold in closed form
+        mm = min((int)sqrt(128.0 * 0.6931471805599453 / -nhl), a.C - 1);
+        mq = min((int)sqrt(256.0 * 0.6931471805599453 / -nhl), a.LT - 1);
+#endif
         if (tid < 2) hband[tid] = 0;
         __syncthreads();
 #pragma unroll
@@ -557,29 +592,31 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
         tab_nhl = nhl;
       }
       // variance k-blocks: those that hold a tau with E(2j - tau) != 0 for a column of the tile,
-      // tau in [2 j0 - hq, 2 (j0 + 63) + hq]; the others multiply T by exact zeros
+      // tau in [2 j0 - hq, 2 (j0 + TW - 1) + hq]; the others multiply T by exact zeros.  (A tile of padding
+      // columns alone, j0 >= C, can have its band past the last tau: it runs the last k-block.)
       int kq_lo = 0, kq_hi = a.LT / 16;
       if (!a.full) {
         const int hq = hband[0];                                 // largest |t| whose E(t) was not flushed
-        const int t_lo = 2 * j0 - hq > 0 ? 2 * j0 - hq : 0;
-        const int t_hi = 2 * (j0 + 63) + hq < a.LT - 1 ? 2 * (j0 + 63) + hq : a.LT - 1;
+        const int t_hi = 2 * (j0 + TW - 1) + hq < a.LT - 1 ? 2 * (j0 + TW - 1) + hq : a.LT - 1;
+        const int t_lo = 2 * j0 - hq > 0 ? (2 * j0 - hq < t_hi ? 2 * j0 - hq : t_hi) : 0;
         // (wave-uniform, and told so: as lane values they made the k loop a divergent one)
         kq_lo = __builtin_amdgcn_readfirstlane(t_lo >> 4);
         kq_hi = __builtin_amdgcn_readfirstlane((t_hi >> 4) + 1);
       }
-      d4 aq[4], am[4];
+      d4 aq[NB], am[NB];
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb) {
+      for (int nb = 0; nb < NB; ++nb) {
         aq[nb] = (d4){0.0, 0.0, 0.0, 0.0};
         am[nb] = (d4){0.0, 0.0, 0.0, 0.0};
       }
       const double* Tq = a.T + ((size_t)o * a.LT + 16 * kq_lo) * a.ldr + i0 + jl;
       // mean k-blocks: the rows are in column order, so the points of the columns
-      // [j0 - hm, j0 + 63 + hm] are the rows cstart[..] .. cstart[..] - 1; H is zero for the others
+      // [j0 - hm, j0 + TW - 1 + hm] are the rows cstart[..] .. cstart[..] - 1; H is zero for the others
       int km_lo = 0, km_hi = a.NP / 16;
       if (!a.full) {
         const int hm = hband[1];
-        const int c_lo = j0 - hm > 0 ? j0 - hm : 0, c_hi = j0 + 64 + hm < a.C ? j0 + 64 + hm : a.C;
+        const int c_hi = j0 + TW + hm < a.C ? j0 + TW + hm : a.C;
+        const int c_lo = j0 - hm > 0 ? (j0 - hm < a.C ? j0 - hm : a.C) : 0;
         km_lo = __builtin_amdgcn_readfirstlane(a.cstart[c_lo] >> 4);
         km_hi = __builtin_amdgcn_readfirstlane((a.cstart[c_hi] + 15) >> 4);
       }
@@ -588,35 +625,57 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
       // for even s, and u >> 1 = hb (s = 0, 1) or hb - 1 (s = 2, 3), hb = LT/2 - 1 - 8 (kq_lo + kb) - 2 g
       // (>= 1)
       const double* pe0 = tabB + (a.LT / 2 - 1 - 8 * kq_lo - 2 * g) + j0 + jl;
-      conv_gemm(Tq, a.ldr, kq_hi - kq_lo, g, aq, [&](int kb, double (&bv)[4][4]) {
+#ifdef BO_ABL_CT_BCONST
+      const double bconst = pe0[0];                              // ablation (timing only): B from a register
+#endif
+      conv_gemm<NB>(Tq, a.ldr, kq_hi - kq_lo, g, aq, [&](int kb, double (&bv)[4][NB]) {
+#ifdef BO_ABL_CT_BCONST
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) bv[s][nb] = bconst;
+#else
         const double* pe = pe0 - 8 * kb;                         // even u
         const double* po = pe + L.HB;                              // odd u
 #pragma unroll
-        for (int nb = 0; nb < 4; ++nb) {
+        for (int nb = 0; nb < NB; ++nb) {
           bv[0][nb] = po[16 * nb];
           bv[1][nb] = pe[16 * nb];
           bv[2][nb] = po[16 * nb - 1];
           bv[3][nb] = pe[16 * nb - 1];
         }
+#endif
       });
       const int* cn0 = cn + 16 * km_lo + 4 * g;
-      if (km_hi > km_lo) conv_gemm(Tm, a.ldr, km_hi - km_lo, g, am, [&](int kb, double (&bv)[4][4]) {
+      if (km_hi > km_lo) conv_gemm<NB>(Tm, a.ldr, km_hi - km_lo, g, am, [&](int kb, double (&bv)[4][NB]) {
+#ifdef BO_ABL_CT_BCONST
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+          for (int nb = 0; nb < NB; ++nb) bv[s][nb] = bconst;
+#else
         const int* c4 = cn0 + 16 * kb;
         const double* ph = tabH + j0 + jl + (a.C - 1);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
           const double* p = ph - c4[s];
 #pragma unroll
-          for (int nb = 0; nb < 4; ++nb) bv[s][nb] = p[16 * nb];
+          for (int nb = 0; nb < NB; ++nb) bv[s][nb] = p[16 * nb];
         }
+#endif
       });
-      mfma_fence<false>(aq[0], aq[1]);
-      mfma_fence<false>(aq[2], aq[3]);
-      mfma_fence<false>(am[0], am[1]);
-      mfma_fence<false>(am[2], am[3]);
+      if constexpr (NB == 1) {
+        mfma_fence<false>(aq[0], am[0]);
+      } else {
+#pragma unroll
+        for (int nb = 0; nb < NB; nb += 2) {
+          mfma_fence<false>(aq[nb], aq[nb + 1]);
+          mfma_fence<false>(am[nb], am[nb + 1]);
+        }
+      }
       const double pv = a.pv[o], pm = a.pm[o];
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb) {
+      for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           // D rows g + 4r, column jl of column block nb
@@ -628,7 +687,7 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
           acq[nb][r] = (o == 0) ? u : acq[nb][r] + u;                       // acquisition.py:108
           const int row = a.row_lo + i0 + g + 4 * r, c = j0 + 16 * nb + jl;
           const long long gi = (long long)row * a.C + c;
-          if (active && i0 + g + 4 * r < a.nrows && c < a.C && gi >= gi_lo && gi < gi_hi) {
+          if (outs && active && i0 + g + 4 * r < a.nrows && c < a.C && gi >= gi_lo && gi < gi_hi) {
             const long long off = (long long)o * a.ld_out + (gi - gi_lo);
             if (a.mu) bo_out_store(a.mu + off, mu);
             if (a.var) bo_out_store(a.var + off, var);
@@ -639,21 +698,26 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
         }
       }
     }
-    // global indices of this lane's 16 candidates (-1: outside the shard)
-    long long gis[4][4];
+    // global indices of this lane's 4 NB candidates (-1: outside the shard)
+    long long gis[NB][4];
 #pragma unroll
-    for (int nb = 0; nb < 4; ++nb) {
+    for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = a.row_lo + i0 + g + 4 * r, c = j0 + 16 * nb + jl;
         const long long gi = (long long)row * a.C + c;
         const bool ok = active && i0 + g + 4 * r < a.nrows && c < a.C && gi >= gi_lo && gi < gi_hi;
         gis[nb][r] = ok ? gi : -1;
-        if (ok && a.acq) bo_out_store(a.acq + (gi - gi_lo), acq[nb][r]);
+        if (outs && ok && a.acq) bo_out_store(a.acq + (gi - gi_lo), acq[nb][r]);
       }
     }
-    if (a.topq > 0) {
-      // the wave's list and the tile's 1024 candidates, merged by rounds of extract-best: each lane
+#ifndef BO_ABL_CT_NOSEL
+    const bool select = a.topq > 0;
+#else
+    const bool select = a.topq > 0 && a.n_lists < 0;             // ablation (timing only): false, and not known to be
+#endif
+    if (select) {
+      // the wave's list and the tile's 256 NB candidates, merged by rounds of extract-best: each lane
       // offers the best of its remaining candidates (and its list entry), the wave takes the best
       // offer (NaN first, then descending, ties by ascending index); a winner that is an evaluated
       // point (the prep launch's hash set, compared exactly) is dropped and the round repeated.
@@ -663,7 +727,7 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
       const long long iq = bo_readlane_i(li, q - 1);
       bool beats = false;
 #pragma unroll
-      for (int nb = 0; nb < 4; ++nb)
+      for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
         for (int r = 0; r < 4; ++r)
           beats = beats || bo_key_before(bo_order_key(acq[nb][r], gis[nb][r]), gis[nb][r], kq, iq);
@@ -677,7 +741,7 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
           long long bi = -1;
           int bs = -1;
 #pragma unroll
-          for (int nb = 0; nb < 4; ++nb) {
+          for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int s = 4 * nb + r;
@@ -718,15 +782,50 @@ __global__ __launch_bounds__(256, 2) void conv_contract_kernel(const ConvArgs a)
     }
   }
   if (a.topq > 0) {
-    if (lane < a.topq) {
-      TopEntry* dst = a.partial + ((size_t)blockIdx.x * 4 + wave) * a.topq;
-      dst[lane].v = lv;
-      dst[lane].i = li;
+    // One list per workgroup: the waves' lists (sorted, the empty entries last) go to LDS over the tables, and the
+    // first wave merges them by q rounds over their heads -- lane w < W offers the head of list w, the wave takes
+    // the best offer (the same order; the indices are distinct, so it is a total one) and that list moves on.
+    const int q = a.topq;
+    TopEntry* ml = (TopEntry*)sd;
+    __syncthreads();                                             // the tables are done with
+    if (lane < q) {
+      ml[wave * q + lane].v = lv;
+      ml[wave * q + lane].i = li;
+    }
+    __syncthreads();
+    if (wave == 0) {
+      int head = 0;
+      double nv = -__builtin_inf();
+      long long ni = -1;
+      for (int r = 0; r < q; ++r) {
+        const bool has = lane < W && head < q;
+        const double hv = has ? ml[lane * q + head].v : -__builtin_inf();
+        const long long hi = has ? ml[lane * q + head].i : -1;
+        const unsigned long long bk = bo_order_key(hv, hi);
+        unsigned long long wk = bk;
+        long long wi = hi;
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+          const unsigned long long ok = __shfl_xor(wk, m, 64);
+          const long long oi = __shfl_xor(wi, m, 64);
+          if (bo_key_before(ok, oi, wk, wi)) { wk = ok; wi = oi; }
+        }
+        if (wk == 0ull) break;                                   // nothing left
+        const bool win = bk == wk && hi == wi;
+        if (win) ++head;
+        const double wv = __shfl(hv, __builtin_ctzll(__ballot(win)), 64);
+        if (lane == r) { nv = wv; ni = wi; }
+      }
+      if (lane < q) {
+        TopEntry* dst = a.partial + (size_t)blockIdx.x * q;
+        dst[lane].v = nv;
+        dst[lane].i = ni;
+      }
     }
     // the lists of the merge that this grid does not fill
     if (blockIdx.x == 0) {
-      const long long e0 = (long long)gridDim.x * 4 * a.topq, e1 = (long long)a.n_lists * a.topq;
-      for (long long e = e0 + tid; e < e1; e += 256) {
+      const long long e0 = (long long)gridDim.x * q, e1 = (long long)a.n_lists * q;
+      for (long long e = e0 + tid; e < e1; e += nt) {
         a.partial[e].v = -__builtin_inf();
         a.partial[e].i = -1;
       }
@@ -774,14 +873,16 @@ ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus) {
   return sc;
 }
 
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st) {
+hipError_t launch_gridconv(const ConvArgs& ca, const ConvPlan& cp, const ConvSched& sc, hipStream_t st) {
   const size_t l1 = ListLds(ca.n, ca.C).bytes, la = AccLds(ca.R).bytes;
-  const size_t l2 = ContractLds(ca.C, ca.Cpad, ca.LT, ca.NP).bytes;
+  const size_t l2 = ContractLds(ca.C, ca.Cpad, ca.LT, ca.NP, cp.waves * ca.topq).bytes;
   if (l1 > kConvLdsBytes || la > kConvLdsBytes) return hipErrorInvalidValue;   // (conv_lds_admits keeps them below)
+  if (cp.waves < 1 || cp.waves > kContractWaves || cp.grid > ca.n_lists) return hipErrorInvalidValue;
+  auto* contract = cp.nb == 4 ? conv_contract_kernel<4> : cp.nb == 2 ? conv_contract_kernel<2> : conv_contract_kernel<1>;
   hipError_t e;
   if ((e = conv_lds_attr(conv_list_kernel, l1)) != hipSuccess) return e;
   if ((e = conv_lds_attr(conv_acc_kernel, la)) != hipSuccess) return e;
-  if ((e = conv_lds_attr(conv_contract_kernel, l2)) != hipSuccess) return e;
+  if ((e = conv_lds_attr(contract, l2)) != hipSuccess) return e;
   const int tau_blocks = (ca.LT + kListWaves - 1) / kListWaves;    // the padding tau too: their pkept
   const long long tm_elems = (long long)ca.NP * ca.ldr;
   const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 512 ? (tm_elems + 1023) / 1024 : 512);
@@ -792,7 +893,7 @@ hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hi
                      (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.pkept,
                      (const int*)ca.ccount, (const int*)ca.clist, ca.ticket, ca.T, sc.nrb, sc.ngrp, sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(conv_contract_kernel, dim3(grid), dim3(256), l2, st, ca);
+  hipLaunchKernelGGL(contract, dim3(cp.grid), dim3(64 * cp.waves), l2, st, ca);
   return hipGetLastError();
 }
 

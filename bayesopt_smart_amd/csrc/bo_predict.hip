@@ -513,7 +513,7 @@ int num_cus() {
 constexpr double kConvMargin = 1.15;
 constexpr int kConvMaxN = 4096;          // (n, m) of a pair in 16 + 16 bits, pair counts below 2^24
 
-void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
+void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem, int cus) {
   if (kmem || !pl->cm || d->cand_kind != BO_CAND_GRID || d->dim != 2 || d->n_cand <= 0) return;
   if (d->mode & (BO_PREDICT_DENSE | BO_PREDICT_NO_SEPARABLE | BO_PREDICT_FP32 | BO_PREDICT_NO_GRID_CONV)) return;
   const char* env = getenv("BO_GRID_CONV");
@@ -544,8 +544,28 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem) {
     if (!(kConvMargin * conv_us < old_us)) return;
   }
   cp.planned = true;
-  const long long wgs = (wave_tiles + 3) / 4;
-  cp.grid = (int)(wgs < pl->grid ? wgs : pl->grid);
+  // The contraction's wave tile, 16 rows x 16 nb columns: the widest that still gives every SIMD two tiles, so
+  // that one wave's epilogue and selection run under another's MFMAs; a grid too small for that takes the
+  // narrowest, which puts a wave on the most SIMDs.  BO_CONV_TILE=1|2|4 (environment, read here like BO_GRID_CONV)
+  // forces nb.  Eight waves per workgroup when that still fills every CU, else four; one workgroup per CU, and no
+  // more workgroups than the merge has lists (a workgroup writes one).
+  const long long tiles64 = wave_tiles;
+  cp.nb = tiles64 >= 8LL * cus ? 4 : 2 * tiles64 >= 8LL * cus ? 2 : 1;
+  const char* tile = getenv("BO_CONV_TILE");
+  if (tile && (tile[0] == '1' || tile[0] == '2' || tile[0] == '4') && tile[1] == 0) cp.nb = tile[0] - '0';
+  const long long tiles = tiles64 * (4 / cp.nb);
+  cp.waves = tiles >= 8LL * cus ? 8 : 4;
+  long long wgs = (tiles + cp.waves - 1) / cp.waves;
+#ifdef BO_ABL_CT_W4
+  // diagnostic build: the other shape with two waves per SIMD, 4-wave workgroups at two per CU (tables built twice)
+  cp.waves = 4;
+  wgs = (tiles + 3) / 4;
+  if (wgs > 2LL * cus) wgs = 2LL * cus;
+#else
+  if (wgs > cus) wgs = cus;
+#endif
+  if (wgs > (long long)pl->grid * pl->waves) wgs = (long long)pl->grid * pl->waves;
+  cp.grid = (int)wgs;
   cp.ws = bo::conv_layout(n, d->n_obj, C, cp.LT, cp.NP, cp.ldr, align256(pl->total));
   pl->total = cp.ws.end;
   pl->conv = cp;
@@ -668,7 +688,7 @@ int make_plan(const bo_predict_desc* d, Plan* pl, bool query_device, bool kmem =
   pl->off_status = pl->off_partial +
                    align256((size_t)1024 * kWaves * (d->topq > 0 ? d->topq : 1) * sizeof(TopEntry));
   pl->total = pl->off_status + 256 + 256;   // +16: separable-K* flag, +32: grid-convolution flag
-  plan_gridconv(d, pl, kmem);
+  plan_gridconv(d, pl, kmem, cus);
   return BO_OK;
 }
 
@@ -962,7 +982,7 @@ static int predict_impl(const bo_predict_desc* d, const double* kstar, long long
   if (pl.conv.planned) {
     // the grid-convolution kernels and the chunk-major kernel are both enqueued; the device flag
     // lets one of them run (no host synchronisation: the call stays capturable)
-    if (bo::launch_gridconv(ca, pl.conv.grid, pa.sched, s) != hipSuccess) return BO_ERR_HIP;
+    if (bo::launch_gridconv(ca, pl.conv, pa.sched, s) != hipSuccess) return BO_ERR_HIP;
   }
   if (kmem) e = launch_kmem(pl, fa, s);
   else if (pl.fp32) switch (pl.dim_pad) {

@@ -82,7 +82,7 @@ struct ConvArgs {
   int row_lo, nrows, ldr;                // grid rows touched by the shard; ldr = nrows padded to 16
   int LT;                                // tau extent 2C - 1 padded to 16 (rows of T)
   int NP;                                // n padded to 16 (rows of Tm)
-  int Cpad;                              // C padded to the wave tile's 64 columns
+  int Cpad;                              // C padded to 64 columns, the widest wave tile (for every tile width)
   int* flag;                             // 0 => every training point is a grid point (the prep launch writes it)
   const double* x;                       // [n][2] training points
   const double* kinv;                    // [n_obj][ld_k][ld_k]
@@ -283,19 +283,22 @@ inline ConvLayout conv_layout(long long n, int n_obj, long long C, long long LT,
 }
 
 // Whether the kernels' LDS tables fit for (n, R, C): the plan's admission test.  The accumulate kernel's
-// schedule on `cus` compute units.  Launch of the sequence behind the prep launch (pair list, accumulate,
-// contraction): `grid` workgroups of the contraction.
+// schedule on `cus` compute units.
 bool conv_lds_admits(int n, int R, int C, int Cpad, int LT, int NP);
 ConvSched conv_acc_schedule(int R, int LT, int ldr, int n_obj, int cus);
-hipError_t launch_gridconv(const ConvArgs& ca, int grid, const ConvSched& sc, hipStream_t st);
 
 // The grid-convolution part of a plan: its dimensions (as in ConvArgs) and workspace layout.
 struct ConvPlan {
   bool planned;          // taken when the device flag allows
-  int grid;              // the contraction kernel's workgroups (<= Plan::grid: it fills the same lists)
+  int nb;                // the contraction's wave tile: 16 rows x 16 nb columns (nb = 4, 2 or 1)
+  int waves;             // waves of a contraction workgroup (4 or 8), a tile each per loop step
+  int grid;              // the contraction kernel's workgroups, a top-q list each (<= the merge's lists)
   int row_lo, nrows, ldr, LT, NP, Cpad;
   ConvLayout ws;
 };
+
+// Launch of the sequence behind the prep launch (pair list, accumulate, contraction).
+hipError_t launch_gridconv(const ConvArgs& ca, const ConvPlan& cp, const ConvSched& sc, hipStream_t st);
 
 // Host-side plan of one bo_predict_acquire call (bo_predict.hip: make_plan).
 struct Plan {
