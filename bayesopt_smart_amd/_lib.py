@@ -73,6 +73,26 @@ class BucbDesc(C.Structure):
     ]
 
 
+class TsDesc(C.Structure):
+    """Mirror of bo_ts_desc (include/bo_amd.h)."""
+
+    _fields_ = [
+        ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
+        ("x_train", c_vp), ("y", c_vp), ("ld_y", C.c_int64), ("kinv", c_vp), ("ld_k", C.c_int64),
+        ("cand_kind", C.c_int32), ("n_samples", C.c_int32),
+        ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
+        ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
+        ("prior_mean", C.c_double * MAX_OBJ), ("prior_var", C.c_double * MAX_OBJ),
+        ("length_scale", C.c_double * MAX_OBJ), ("jitter", C.c_double),
+        ("n_features", C.c_int64),
+        ("z", c_vp), ("phase", c_vp), ("theta", c_vp), ("eps", c_vp),
+        ("paths", c_vp), ("ld", C.c_int64), ("weights_out", c_vp),
+    ]
+
+
+TS_MAX_FEATURES = 65536
+
+
 class PowellResult(C.Structure):
     """Mirror of bo_powell_result (include/bo_amd.h)."""
 
@@ -135,6 +155,8 @@ _SIGS = {
                                             C.c_size_t, c_vp]),
     "bo_select_batch_bucb_workspace_size": (C.c_size_t, [C.POINTER(BucbDesc)]),
     "bo_select_batch_bucb": (C.c_int, [C.POINTER(BucbDesc), c_vp, C.c_size_t, c_vp]),
+    "bo_sample_paths_workspace_size": (C.c_size_t, [C.POINTER(TsDesc)]),
+    "bo_sample_paths": (C.c_int, [C.POINTER(TsDesc), c_vp, C.c_size_t, c_vp]),
     "bo_pareto_mask": (C.c_int, [c_vp, C.c_int64, C.c_int32, c_vp, c_vp]),
     "bo_hvi_boxes": (C.c_int, [c_dbl_p, C.c_int64, C.c_int32, c_dbl_p, c_vp, C.c_int64,
                                C.POINTER(C.c_int64)]),

@@ -409,7 +409,7 @@ def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, 
     return idx[idx >= 0]
 
 
-BATCH_STRATEGIES = ("top", "bucb")
+BATCH_STRATEGIES = ("top", "bucb", "ts")
 
 
 def select_batch_bucb(std_mu_objectives, variance_objectives, x_train, kinv, cands, prior_variance,
@@ -512,3 +512,187 @@ def update_hypervolume_improvement_exact(acquisition_values, ucb, y_vector, n_ev
         front = front.cpu().numpy()
     hypervolume_improvement_exact(ucb, front, reference_point, prior_mean, prior_variance,
                                   out=acquisition_values)
+
+
+# ------------------------------------------------- Thompson-sampling batches (pathwise draws)
+def thompson_draws(rng, n_obj, dim, n_train, n_samples, n_features):
+    """The random numbers of bo_sample_paths from a numpy.random.Generator `rng` (never numpy's
+    global RNG: config.py seeds that one and the LHS design depends on its draw order):
+    (Z [n_obj, D, dim] standard normals, B [n_obj, D] uniform on [0, 2 pi), Theta [S, n_obj, D] and
+    E [S, n_obj, N] standard normals), float64, in this order of draws."""
+    if not isinstance(rng, np.random.Generator):
+        raise TypeError("thompson_draws needs a numpy.random.Generator (numpy.random.default_rng(seed))")
+    z = rng.standard_normal((n_obj, n_features, dim))
+    b = rng.uniform(0.0, 2.0 * np.pi, (n_obj, n_features))
+    theta = rng.standard_normal((n_samples, n_obj, n_features))
+    eps = rng.standard_normal((n_samples, n_obj, n_train))
+    return z, b, theta, eps
+
+
+def sample_paths(x_train, y_train, kinv, cands, prior_mean, prior_variance, length_scales, draws, offset=0,
+                 count=None, float_type=None, jitter=None, ld=None, return_weights=False, device=None):
+    """Posterior function draws over the shard [offset, offset + count) of `cands` by pathwise
+    conditioning over random Fourier features (bo_sample_paths; include/bo_amd.h states the
+    definition).  x_train [N, d], y_train [N, n_obj], kinv [n_obj, >= N, >= N]: the fitted state
+    the predict uses; draws = (Z, B, Theta, E) as thompson_draws returns them (numpy or device).
+    jitter defaults to KERNEL_JITTER of `float_type`'s branch.  Returns the device tensor
+    [S, n_obj, count] of the standardised draws (f - prior_mean) / sqrt(prior_variance) (a view of
+    [S, n_obj, ld] when `ld` is given) -- with `return_weights`, also the weights v [S, n_obj, N]
+    that were used.  Deterministic: the same arguments give the same bits."""
+    from .config import precision_constants
+    dev = require_device(device) if device is not None else _dev_of(kinv, x_train)
+    x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
+    y = torch.as_tensor(y_train, dtype=F64, device=dev)
+    kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
+    n, n_obj = x.shape[0], kinv.shape[0]
+    if y.dim() != 2 or y.stride(1) != 1:
+        y = y.contiguous()
+    z, b, theta, eps = (torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, np.ndarray) else a,
+                                        dtype=F64, device=dev).contiguous() for a in draws)
+    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[1] != kinv.shape[2] \
+            or kinv.shape[1] < n or y.shape[0] < n or y.shape[1] < n_obj:
+        raise ValueError("x_train must be [N, d], y_train [N, n_obj] and kinv [n_obj, >=N, >=N]")
+    if theta.dim() != 3 or z.dim() != 3:
+        raise ValueError("draws must be (Z [n_obj, D, d], B [n_obj, D], Theta [S, n_obj, D], E [S, n_obj, N])")
+    n_samples, n_feat = theta.shape[0], theta.shape[2]
+    if tuple(z.shape) != (n_obj, n_feat, cands.dim) or tuple(b.shape) != (n_obj, n_feat) \
+            or theta.shape[1] != n_obj or tuple(eps.shape) != (n_samples, n_obj, n):
+        raise ValueError("draws must be (Z [n_obj, D, d], B [n_obj, D], Theta [S, n_obj, D], E [S, n_obj, N])")
+    if not 1 <= n_samples <= _lib.MAX_TOPQ:
+        raise ValueError(f"sample_paths handles 1 <= n_samples <= {_lib.MAX_TOPQ}")
+    count = int(cands.n - offset if count is None else count)
+    ld = count if ld is None else int(ld)
+    d = _lib.TsDesc()
+    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.x_train, d.y, d.ld_y = x.data_ptr(), y.data_ptr(), y.stride(0)
+    d.kinv, d.ld_k = kinv.data_ptr(), kinv.shape[-1]
+    d.cand_kind, d.n_samples, d.n_features = cands.kind_code, n_samples, n_feat
+    d.n_cand, d.cand_offset = count, offset
+    if cands.kind == "grid":
+        for k in range(cands.dim):
+            d.grid_lo[k] = cands.lo[k]
+            d.grid_shape[k] = cands.shape[k]
+    elif cands.kind == "sobol":
+        d.cand = cands.cand_arg
+    else:                                              # explicit candidates: the shard's rows
+        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    for o in range(n_obj):
+        d.prior_mean[o] = float(prior_mean[o])
+        d.prior_var[o] = float(prior_variance[o])
+        d.length_scale[o] = float(length_scales[o])
+    d.jitter = float(precision_constants(float_type)[0] if jitter is None else jitter)
+    d.z, d.phase, d.theta, d.eps = z.data_ptr(), b.data_ptr(), theta.data_ptr(), eps.data_ptr()
+    paths = torch.empty((n_samples, n_obj, ld), dtype=F64, device=dev)
+    d.paths, d.ld = paths.data_ptr(), ld
+    wts = None
+    if return_weights:
+        wts = torch.empty((n_samples, n_obj, n), dtype=F64, device=dev)
+        d.weights_out = wts.data_ptr()
+    lib = _lib.load()
+    nbytes = lib.bo_sample_paths_workspace_size(d)
+    if nbytes == 0:
+        raise _lib.BoNativeError(_lib.ERR_ARG, "bo_sample_paths_workspace_size")
+    ws = Workspace.get(nbytes, dev)
+    _lib.check(lib.bo_sample_paths(d, ws.data_ptr(), ws.numel(), stream_handle(dev)), "bo_sample_paths")
+    out = paths[:, :, :count]
+    return (out, wts) if return_weights else out
+
+
+def resolve_ts_picks(lists):
+    """Pick s = the first index of lists[s] (draw s's candidates, best first; negative = empty) that
+    no earlier draw picked; -1 when none is left.  int64 [len(lists)]."""
+    picks, taken = [], set()
+    for idx in lists:
+        p = -1
+        for i in idx:
+            i = int(i)
+            if i >= 0 and i not in taken:
+                p = i
+                break
+        if p >= 0:
+            taken.add(p)
+        picks.append(p)
+    return np.asarray(picks, dtype=np.int64)
+
+
+def select_batch_ts(x_train, y_train, kinv, cands, prior_mean, prior_variance, length_scales, draws,
+                    evaluated_points, batch_size, acquisition="sum_ucb", y_evaluated=None, reference_point=None,
+                    offset=0, count=None, mask=None, float_type=None, jitter=None, group=None,
+                    return_details=False):
+    """A Thompson-sampling batch: pick s is the best candidate of posterior draw s (sample_paths)
+    under the acquisition -- "sum_ucb": the sum over the objectives of the standardised draw, the
+    reference's scalarisation (acquisition.py:89-108) with the UCB replaced by the draw; "hvi": the
+    exact hypervolume improvement of the drawn objective vector over the Pareto front of
+    `y_evaluated` above `reference_point` (the TSEMO criterion) -- among the candidates that are
+    neither evaluated nor picked by an earlier draw (select_next_batch's order).  NOT in the
+    reference.  Draw s runs the existing masked selection with top-(s + 1), which always holds a
+    candidate no earlier draw took; every record goes into one device block, read back once, and
+    the picks are resolved in draw order on the host.  With collectives on, each draw's records are
+    exchanged (exchange_topq_rec) and resolved on the merged lists: every rank scores the same draws
+    (the caller hands every rank the same `draws`), so the picks are identical on every rank.
+    Returns the global indices of the picks (fewer than batch_size when the candidates run out);
+    `return_details`: a dict (picks with -1 markers [batch_size], paths, and per draw the record's
+    indices `lists` and values `vals`)."""
+    if acquisition not in ("sum_ucb", "hvi"):
+        raise ValueError(f"select_batch_ts: acquisition {acquisition!r} has no sampled form "
+                         "(expected 'sum_ucb' or 'hvi')")
+    if not 1 <= batch_size <= _lib.MAX_TOPQ:
+        raise ValueError(f"select_batch_ts handles 1 <= batch_size <= {_lib.MAX_TOPQ}")
+    if np.shape(draws[2])[0] != batch_size:
+        raise ValueError("select_batch_ts: draws must hold batch_size samples")
+    count = int(cands.n - offset if count is None else count)
+    paths = sample_paths(x_train, y_train, kinv, cands, prior_mean, prior_variance, length_scales, draws,
+                         offset=offset, count=count, float_type=float_type, jitter=jitter)
+    dev = paths.device
+    n_obj = paths.shape[1]
+    if mask is None:
+        mask = ExclusionMask(cands, offset, count, dev)
+    elif mask.offset != offset or mask.count != count:
+        raise ValueError("select_batch_ts: the mask covers another shard")
+    mask.update(evaluated_points)
+    lib = _lib.load()
+    st = stream_handle(dev)
+    ws = Workspace.get(lib.bo_select_topq_workspace_size(count, batch_size), dev)
+    acq = torch.empty(count, dtype=F64, device=dev)
+    # draw s's record: s + 1 values, then s + 1 bit-cast int64 indices, at doubles [s (s + 1), ...)
+    rec = torch.empty(batch_size * (batch_size + 1), dtype=F64, device=dev)
+    if acquisition == "hvi":
+        from .pareto import is_pareto_efficient
+        yv = np.asarray(y_evaluated, dtype=np.float64)
+        front = yv[is_pareto_efficient(yv)] if len(yv) else np.zeros((0, n_obj))
+        boxes = torch.as_tensor(hypervolume_boxes(front, reference_point), device=dev)
+        shift = _host_vec(prior_mean, n_obj)
+        scale = _host_vec(np.sqrt(np.asarray(prior_variance, dtype=np.float64)), n_obj)
+    for s in range(batch_size):
+        q = s + 1
+        tv = rec.data_ptr() + 8 * s * (s + 1)
+        ti = tv + 8 * q
+        p = paths[s]
+        if acquisition == "sum_ucb":
+            _lib.check(lib.bo_update_hypervolume_improvement(acq.data_ptr(), p.data_ptr(), n_obj, count, st),
+                       "bo_update_hypervolume_improvement")
+            _lib.check(lib.bo_select_topq_masked(acq.data_ptr(), count, offset, mask.ptr, q, tv, ti,
+                                                 ws.data_ptr(), ws.numel(), st), "bo_select_topq_masked")
+        else:
+            _lib.check(lib.bo_hvi_select_topq_masked(acq.data_ptr(), p.data_ptr(), p.stride(0), count, n_obj,
+                                                     shift, scale, boxes.data_ptr() if boxes.numel() else None,
+                                                     boxes.shape[0], offset, mask.ptr, q, tv, ti, ws.data_ptr(),
+                                                     ws.numel(), st), "bo_hvi_select_topq_masked")
+    from .distributed import collectives_on, exchange_topq_rec
+    lists, vals = [], []
+    if collectives_on(group):
+        for s in range(batch_size):
+            q = s + 1
+            v, i = exchange_topq_rec(rec[s * q: s * q + 2 * q], q, group)
+            vals.append(np.asarray(v, dtype=np.float64))
+            lists.append(np.asarray(i, dtype=np.int64))
+    else:
+        host = rec.cpu().numpy()                     # the one read-back
+        for s in range(batch_size):
+            q = s + 1
+            vals.append(host[s * q: s * q + q].copy())
+            lists.append(host[s * q + q: s * q + 2 * q].view(np.int64).copy())
+    picks = resolve_ts_picks(lists)
+    if return_details:
+        return {"picks": picks, "paths": paths, "lists": lists, "vals": vals}
+    return picks[picks >= 0]

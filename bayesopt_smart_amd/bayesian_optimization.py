@@ -30,8 +30,8 @@ import torch
 
 from . import kernels as K
 from .acquisition import (BATCH_STRATEGIES, ExclusionMask, ehvi_select_indices, hvi_select_indices,
-                          select_batch_bucb, select_indices, update_expected_hypervolume_improvement,
-                          update_hypervolume_improvement_exact)
+                          select_batch_bucb, select_batch_ts, select_indices, thompson_draws,
+                          update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
 
 ACQUISITIONS = ("sum_ucb", "hvi", "ehvi")
 
@@ -128,7 +128,8 @@ class DeviceBackend:
     with the float32 jitters (numba_kernels.py:290-302), invert_k adds 1e-3, and the predict runs
     the f32 matrix-core kernel (mode "fp32") with the variance floor 1e-6."""
 
-    def __init__(self, cands, n_obj, total_samples, device=None, buffers=None, group=None, float_type=None):
+    def __init__(self, cands, n_obj, total_samples, device=None, buffers=None, group=None, float_type=None,
+                 ts_features=1024, ts_seed=0):
         from .distributed import shard_range
         self.dev = require_device(device)
         self.float_type = resolve_float_type(float_type)
@@ -143,6 +144,11 @@ class DeviceBackend:
         self._lu_hint = None           # per objective: the previous invert_k took the LU path
         self.inverse_paths = []
         self._excl_mask = None         # the shard's ExclusionMask (exact-HVI selection)
+        # batch_strategy "ts": one generator per backend, drawn from anew every iteration.  Every
+        # rank constructs the same generator and draws the same numbers in the same order, so the
+        # ranks score the same posterior draws without a collective for them.
+        self.ts_features = int(ts_features)
+        self._ts_rng = np.random.default_rng(ts_seed)
 
     def fit(self, x_vector, y_vector, n, prior_mean, prior_variance, length_scales):
         """Returns (Powell's OptimizeResult, fitted device state, time after the Powell fit)."""
@@ -221,7 +227,11 @@ class DeviceBackend:
         batch_strategy "top" is the reference's batch (the batch_size best values of one
         acquisition array); "bucb" (not in the reference) takes every pick after the first from the
         UCB recomputed with the variance conditioned on the earlier picks
-        (acquisition.select_batch_bucb), over this process's shard."""
+        (acquisition.select_batch_bucb), over this process's shard; "ts" (not in the reference)
+        takes pick s as the best candidate of posterior draw s (Thompson sampling by pathwise
+        conditioning, acquisition.select_batch_ts) for "sum_ucb" and "hvi", with any number of
+        ranks: the draws come from this backend's generator (ts_seed), the same on every rank, so no
+        collective is needed for them and the exchange of the top-q records merges the shards."""
         _check_acquisition(acquisition)
         _check_batch_strategy(batch_strategy, acquisition, batch_size, self.group)
         xd, yd, kinv = fitted
@@ -236,6 +246,19 @@ class DeviceBackend:
                                      self.cands, prior_variance, length_scales, betas, evaluated, batch_size,
                                      offset=self.offset, count=self.count, mask=self._excl_mask,
                                      float_type=self.float_type)
+        if batch_strategy == "ts":
+            # the predict still runs (topq = 0): the callbacks' state arrays are filled
+            predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
+                            outputs=tuple(out), topq=0, offset=self.offset, count=self.count, out=out,
+                            device=self.dev, mode=self.mode, float_type=self.float_type)
+            if self._excl_mask is None:
+                self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
+            draws = thompson_draws(self._ts_rng, len(prior_mean), self.cands.dim, xd.shape[0], batch_size,
+                                   self.ts_features)
+            return select_batch_ts(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, draws,
+                                   evaluated, batch_size, acquisition=acquisition, y_evaluated=y_evaluated,
+                                   reference_point=reference_point, offset=self.offset, count=self.count,
+                                   mask=self._excl_mask, float_type=self.float_type, group=self.group)
         if acquisition == "sum_ucb" and batch_size <= _lib.MAX_TOPQ:
             from .distributed import sharded_predict_acquire
             _, (_, idx) = sharded_predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance,
@@ -299,7 +322,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
              n_objectives, function, betas, length_scales, batch_size, bounds,
              callbacks: Optional[List[Callable]] = None, *,
              acquisition: str = "sum_ucb", group=None, backend=None,
-             float_type=None, batch_strategy: str = "top") -> Tuple[np.ndarray, np.ndarray, int]:
+             float_type=None, batch_strategy: str = "top", ts_features: int = 1024,
+             ts_seed: int = 0) -> Tuple[np.ndarray, np.ndarray, int]:
     """bayesian_optimization.py:51-247 with the reference's argument list.
 
     `kernel_matrices` and the posterior arrays may be HIP tensors (in place) or numpy arrays;
@@ -315,7 +339,11 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     fit / select / state_arrays / cands / rank / world / bufs).  `float_type` np.float32 runs the
     reference's float32 branch (DeviceBackend).  `batch_strategy` "bucb" selects each batch by
     hallucinated observations (DeviceBackend.select; one rank, acquisition "sum_ucb",
-    batch_size <= BO_MAX_TOPQ); "top", the default, is the reference's batch.
+    batch_size <= BO_MAX_TOPQ); "ts" by Thompson sampling over pathwise posterior draws
+    (acquisition "sum_ucb" or "hvi", any number of ranks, batch_size <= BO_MAX_TOPQ), with
+    `ts_features` random Fourier features and the draws of default_rng(`ts_seed`) -- every rank
+    constructs the same generator, so no collective is needed for the draws (both are the
+    backend's when `backend` is given); "top", the default, is the reference's batch.
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -345,7 +373,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         bufs.std_variance_objectives = dev_buf(std_variance_objectives, (n_obj, cnt))
         bufs.ucb = dev_buf(ucb, (n_obj, cnt))
         bufs.acquisition_values = dev_buf(acquisition_values, (cnt,))
-        backend = DeviceBackend(cands, n_obj, total_samples, dev, bufs, group, float_type=float_type)
+        backend = DeviceBackend(cands, n_obj, total_samples, dev, bufs, group, float_type=float_type,
+                                ts_features=ts_features, ts_seed=ts_seed)
     cands, rank, world = backend.cands, backend.rank, backend.world
     gather = bool(callbacks)
     bgroup = getattr(backend, "group", group)
@@ -420,9 +449,16 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
 
 
 def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
-    """What batch_strategy="bucb" does not cover raises here, with the reason."""
+    """What batch_strategy="bucb" / "ts" do not cover raises here, with the reason."""
     if batch_strategy not in BATCH_STRATEGIES:
-        raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top' or 'bucb')")
+        raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top', 'bucb' or 'ts')")
+    if batch_strategy == "ts":
+        if acquisition not in ("sum_ucb", "hvi"):
+            raise ValueError("batch_strategy='ts' scores posterior draws; acquisition='ehvi' integrates over "
+                             f"the posterior and has no sampled form (got acquisition={acquisition!r})")
+        if batch_size > _lib.MAX_TOPQ:
+            raise ValueError(f"batch_strategy='ts' supports batch_size <= {_lib.MAX_TOPQ} (got {batch_size})")
+        return
     if batch_strategy != "bucb":
         return
     if acquisition != "sum_ucb":
@@ -478,7 +514,11 @@ class BayesianOptimization:
     f32 matrix cores) and ``initial_points`` ([n0, d] points evaluated as the initial design
     instead of the Latin hypercube) and ``batch_strategy`` ("top", the reference's batch: the
     batch_size best acquisition values; or "bucb": every pick after the first accounts for the
-    earlier ones through hallucinated observations, acquisition.select_batch_bucb).
+    earlier ones through hallucinated observations, acquisition.select_batch_bucb; or "ts": pick s
+    is the best candidate of posterior draw s, acquisition.select_batch_ts, with ``ts_features``
+    random Fourier features, default 1024, and the draws of numpy.random.default_rng(``ts_seed``),
+    default 0 -- every rank constructs the same generator and draws anew every iteration, so the
+    ranks need no collective for the draws).
     With several ranks, each holds its shard of the posterior arrays, the initial design is drawn
     and evaluated on rank 0 (every rank draws the same RNG numbers, so the RNG stays in step) and
     broadcast, and the loop runs as `optimize` describes.
@@ -522,12 +562,17 @@ class BayesianOptimization:
         self.acquisition = kwargs.get("acquisition", "sum_ucb")
         _check_acquisition(self.acquisition)
         self.batch_strategy = kwargs.get("batch_strategy", "top")
+        self.ts_features = int(kwargs.get("ts_features", 1024))
+        self.ts_seed = kwargs.get("ts_seed", 0)
+        if not 1 <= self.ts_features <= _lib.TS_MAX_FEATURES:
+            raise ValueError(f"ts_features must be in [1, {_lib.TS_MAX_FEATURES}] (got {self.ts_features})")
         _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
                       self.batch_strategy, self.group)
         self.x_vector = np.zeros((self.total_samples, self.dim), dtype=ft)
         self.y_vector = np.zeros((self.total_samples, n_objectives), dtype=ft)
         self._backend = DeviceBackend(self.candidates, n_objectives, self.total_samples, self.device,
-                                      group=self.group, float_type=ft)
+                                      group=self.group, float_type=ft, ts_features=self.ts_features,
+                                      ts_seed=self.ts_seed)
         self._buffers = self._backend.bufs
         self.k_star = None   # never materialised (the reference allocates n_obj x T x M here)
         rank, world = _world(self.group)
@@ -584,7 +629,8 @@ class BayesianOptimization:
             betas=self.betas, length_scales=self.length_scales, batch_size=self.batch_size,
             bounds=self.bounds, callbacks=self.callbacks if self.callbacks else None,
             acquisition=self.acquisition, group=self.group, backend=self._backend,
-            float_type=self.float_type, batch_strategy=self.batch_strategy)
+            float_type=self.float_type, batch_strategy=self.batch_strategy, ts_features=self.ts_features,
+            ts_seed=self.ts_seed)
 
     def pareto_analysis(self) -> np.ndarray:
         """bayesian_optimization.py:465-488."""

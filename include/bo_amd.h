@@ -303,6 +303,64 @@ size_t bo_select_batch_bucb_workspace_size(const bo_bucb_desc* desc);
 int bo_select_batch_bucb(const bo_bucb_desc* desc, void* workspace, size_t workspace_bytes,
                          void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Posterior function draws for Thompson-sampling batches: pathwise conditioning (Wilson et al.
+ * 2020) over a random-Fourier-feature prior.  NOT in the reference.  Per objective o and draw s,
+ * with x0 = training row 0 (the centre the predict uses), l = length_scale, pv = prior_var,
+ * pm = prior_mean, D = n_features, N = n_train and the caller's random numbers
+ *   Z [n_obj][D][dim], E [S][n_obj][N], Theta [S][n_obj][D]  standard normals,
+ *   B [n_obj][D]                                             uniform on [0, 2 pi):
+ *   w_oi     = Z_oi / l_o
+ *   phi_oi(c) = sqrt(2 pv_o / D) cos(w_oi . (c - x0) + B_oi)          feature i of the prior
+ *   g_so(c)  = sum_i Theta_soi phi_oi(c)                               prior draw
+ *   r_so     = y_o - pm_o - g_so(X) - sqrt(jitter) E_so                [N]
+ *   v_so     = kinv_o r_so                                             [N]
+ *   f_so(c)  = pm_o + g_so(c) + sum_n k_o(c, x_n) v_son                the posterior draw
+ *   z_so(c)  = (f_so(c) - pm_o) / sqrt(pv_o)                           `paths`, standardised like std_mu
+ * For fixed (Z, B) the mean of f over (Theta, E) is exactly the posterior mean
+ * pm + k kinv (y - pm); at a training point f_so(x_n) = y_on - sqrt(jitter) E_son - jitter v_son.
+ * The call is a deterministic function of its arguments (no random numbers are drawn inside; a
+ * workspace of any content gives the same bits), asynchronous on its stream, without host
+ * synchronisation, capturable in a HIP graph.  The value of a candidate does not depend on the
+ * shard (n_cand, cand_offset) it is computed in.  paths[s] takes the place of the `ucb` array of
+ * bo_update_hypervolume_improvement / bo_hvi_select_topq_masked (shift = prior_mean, scale =
+ * sqrt(prior_var)): the best candidate of draw s is pick s of the batch.
+ * Fields shared with bo_bucb_desc have its meaning.  n_features <= BO_TS_MAX_FEATURES (any value,
+ * not only multiples of 4); n_cand <= 2^36. */
+#define BO_TS_MAX_FEATURES 65536
+typedef struct bo_ts_desc {
+  int32_t n_obj;              /* objectives (<= BO_MAX_OBJ)                                   */
+  int32_t dim;                /* input dimensions (<= BO_MAX_DIM)                              */
+  int64_t n_train;            /* N >= 1                                                       */
+  const double* x_train;      /* device [n_train][dim]                                        */
+  const double* y;            /* device, rows [n_obj] with row stride ld_y                    */
+  int64_t ld_y;               /* >= n_obj                                                     */
+  const double* kinv;         /* device [n_obj][ld_k][ld_k]; leading N x N block = invert_k() */
+  int64_t ld_k;
+  int32_t cand_kind;          /* bo_cand_kind                                                 */
+  int32_t n_samples;          /* S, 1 .. BO_MAX_TOPQ                                          */
+  const void* cand;           /* device [n_cand][dim] (kinds I64/F64); host bo_sobol_desc* (SOBOL) */
+  int64_t n_cand;             /* candidates of this call (a shard)                            */
+  int64_t cand_offset;        /* global index of this call's first candidate                  */
+  int64_t grid_lo[BO_MAX_DIM];     /* kind GRID                                              */
+  int64_t grid_shape[BO_MAX_DIM];  /* kind GRID (axis dim-1 fastest)                         */
+  double prior_mean[BO_MAX_OBJ];
+  double prior_var[BO_MAX_OBJ];
+  double length_scale[BO_MAX_OBJ];
+  double jitter;              /* KERNEL_JITTER added by invert_k: 1e-6 (1e-3 float32 branch)  */
+  int64_t n_features;         /* D, 1 .. BO_TS_MAX_FEATURES                                   */
+  const double* z;            /* device [n_obj][D][dim]                                       */
+  const double* phase;        /* device [n_obj][D]                                            */
+  const double* theta;        /* device [S][n_obj][D]                                         */
+  const double* eps;          /* device [S][n_obj][N]                                         */
+  double* paths;              /* device [S][n_obj][ld]: z_so, columns [0, n_cand) written     */
+  int64_t ld;                 /* row stride of paths (>= n_cand)                              */
+  double* weights_out;        /* optional device [S][n_obj][N]: the v that was used           */
+} bo_ts_desc;
+/* bytes of device workspace bo_sample_paths needs for `desc` (0 on bad args) */
+size_t bo_sample_paths_workspace_size(const bo_ts_desc* desc);
+int bo_sample_paths(const bo_ts_desc* desc, void* workspace, size_t workspace_bytes, void* stream);
+
 /* is_pareto_efficient  bayesopt/pareto.py:12-45: mask[i] = 1 iff no row j dominates row i
  * (maximisation, weak dominance; NaN rows never dominate nor are dominated).
  * y: device [n][n_obj] row-major; mask: device uint8 [n]. Bit-exact. */
