@@ -73,6 +73,26 @@ class BucbDesc(C.Structure):
     ]
 
 
+class KbDesc(C.Structure):
+    """Mirror of bo_kb_desc (include/bo_amd.h)."""
+
+    _fields_ = [
+        ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
+        ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
+        ("cand_kind", C.c_int32), ("q", C.c_int32),
+        ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
+        ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
+        ("prior_var", C.c_double * MAX_OBJ), ("length_scale", C.c_double * MAX_OBJ),
+        ("jitter", C.c_double), ("min_variance", C.c_double),
+        ("mu", c_vp), ("var", c_vp), ("ld", C.c_int64), ("mask", c_vp),
+        ("front", c_vp), ("n_front", C.c_int64), ("ref_point", C.c_double * 4),
+        ("form", C.c_int32), ("reserved", C.c_int32), ("box_capacity", C.c_int64),
+        ("host_ws", c_vp), ("host_ws_bytes", C.c_size_t),
+        ("top_val", c_vp), ("top_idx", c_vp), ("believed", c_vp), ("var_out", c_vp),
+        ("acq_first", c_vp), ("acq_last", c_vp), ("n_boxes_max", C.POINTER(C.c_int64)),
+    ]
+
+
 class TsDesc(C.Structure):
     """Mirror of bo_ts_desc (include/bo_amd.h)."""
 
@@ -155,7 +175,10 @@ _SIGS = {
                                             C.c_size_t, c_vp]),
     "bo_select_batch_bucb_workspace_size": (C.c_size_t, [C.POINTER(BucbDesc)]),
     "bo_select_batch_bucb": (C.c_int, [C.POINTER(BucbDesc), c_vp, C.c_size_t, c_vp]),
-    "bo_sample_paths_workspace_size": (C.c_size_t, [C.POINTER(TsDesc)]),
+    "bo_select_batch_kb_workspace_size": (C.c_size_t, [C.POINTER(KbDesc)]),
+    "bo_select_batch_kb_host_workspace_size": (C.c_size_t, [C.POINTER(KbDesc)]),
+    "bo_select_batch_kb": (C.c_int, [C.POINTER(KbDesc), c_vp, C.c_size_t, c_vp]),
+    "bo_sample_paths_workspace_size":(C.c_size_t, [C.POINTER(TsDesc)]),
     "bo_sample_paths": (C.c_int, [C.POINTER(TsDesc), c_vp, C.c_size_t, c_vp]),
     "bo_pareto_mask": (C.c_int, [c_vp, C.c_int64, C.c_int32, c_vp, c_vp]),
     "bo_hvi_boxes": (C.c_int, [c_dbl_p, C.c_int64, C.c_int32, c_dbl_p, c_vp, C.c_int64,

@@ -500,6 +500,159 @@ def select_batch_bucb(std_mu_objectives, variance_objectives, x_train, kinv, can
     return (idx, var_out[:, :count]) if return_variance else idx
 
 
+ALL_BATCH_STRATEGIES = BATCH_STRATEGIES + ("kb",)      # "kb": with acquisition="ehvi" only
+
+
+class PinnedStaging:
+    """Grow-only pinned host buffer, one per (device, stream), cached like Workspace: the staging
+    block of select_batch_kb (bo_select_batch_kb hands it back on return, so the next call on
+    the stream may rewrite it)."""
+
+    _cache = {}
+
+    @classmethod
+    def get(cls, nbytes, device, stream=None):
+        st = stream_handle(device) if stream is None else stream
+        key = (device.type, device.index, int(st or 0))
+        buf = cls._cache.get(key)
+        if buf is None or buf.numel() < nbytes:
+            size = max(int(nbytes), 0 if buf is None else buf.numel() + buf.numel() // 2, 4096)
+            buf = torch.empty(size, dtype=torch.uint8, pin_memory=True)
+            cls._cache[key] = buf
+        return buf
+
+
+_KB_BOX_CAPACITY = {}          # n_obj -> the box capacity the last call needed
+
+
+def select_batch_kb(mu_objectives, variance_objectives, x_train, kinv, cands, prior_variance, length_scales,
+                    y_vector, n_evaluations, reference_point, evaluated_points, batch_size, offset=0, count=None,
+                    mask=None, float_type=None, jitter=None, min_variance=None, form="auto", acq_out=None,
+                    return_details=False, box_capacity=None):
+    """A batch for the EHVI whose later picks account for the earlier ones (Kriging believer,
+    Ginsbourger, Le Riche & Carraro 2010; bo_select_batch_kb, include/bo_amd.h states the
+    definition).  NOT in the reference.  Pick t is the best candidate of the EHVI of
+    (mu, var conditioned on picks 1..t-1) over the Pareto front of y_vector[:n_evaluations]
+    extended by the posterior means at those picks (the believed observations; the mean does not
+    move); the first pick is ehvi_select_indices' top-1.
+
+    mu_objectives / variance_objectives: the predict's outputs in objective units over the shard
+    [offset, offset + count) of `cands` (device [n_obj, >= count], not modified); x_train [N, d]
+    and kinv [n_obj, N, N] the fitted state the predict used.  `mask`: this shard's ExclusionMask,
+    updated here with evaluated_points; without one a mask is built for the call.  jitter /
+    min_variance default to KERNEL_JITTER / MIN_VARIANCE of `float_type`'s branch.  `form`: "auto",
+    "direct" or "table" as expected_hypervolume_improvement's (same bits).  `acq_out` (device
+    [count]) receives the first pick's acquisition, the plain EHVI array.  The box decomposition
+    runs on the host between the picks, so the call synchronises with the stream once per pick
+    (pinned staging and the device workspace are cached); when a pick's boxes exceed the device
+    buffers (`box_capacity`, default: what the last call needed, at least 1024) the call is
+    repeated from the start with the reported count rounded up -- the picks are deterministic.
+    Returns the global indices of the picks (fewer than batch_size when the shard runs out of
+    candidates); with `return_details`, a dict (top_idx, top_val, var, acq_first, acq_last,
+    believed: device tensors; n_boxes_max: int)."""
+    from .config import precision_constants
+    if not 1 <= batch_size <= _lib.MAX_TOPQ:
+        raise ValueError(f"select_batch_kb handles 1 <= batch_size <= {_lib.MAX_TOPQ}")
+    if form not in EHVI_FORMS:
+        raise ValueError(f"unknown form {form!r} (expected 'auto', 'direct' or 'table')")
+    dev = _dev_of(mu_objectives, variance_objectives)
+    mu = _Arg(mu_objectives, dev)
+    var = _Arg(variance_objectives, dev)
+    n_obj = mu.t.shape[0]
+    if n_obj > 4:
+        raise ValueError(f"select_batch_kb supports at most 4 objectives (got {n_obj})")
+    count = int(cands.n - offset if count is None else count)
+    if mu.t.dim() != 2 or var.t.shape != mu.t.shape or mu.t.shape[1] < count or mu.t.stride(1) != 1 \
+            or var.t.stride() != mu.t.stride():
+        raise ValueError("mu / variance must be [n_obj, >= count] with one row stride")
+    x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
+    kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
+    n = x.shape[0]
+    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[0] != n_obj \
+            or kinv.shape[1] != kinv.shape[2] or kinv.shape[1] < n:
+        raise ValueError("x_train must be [N, d] and kinv [n_obj, >=N, >=N]")
+    ref = np.asarray(reference_point, dtype=np.float64).ravel()
+    if ref.size != n_obj:
+        raise ValueError(f"the reference point has {ref.size} objectives, mu {n_obj}")
+    front = np.ascontiguousarray(np.asarray(_front_of(y_vector, n_evaluations, ref), dtype=np.float64)
+                                 .reshape(-1, n_obj))
+    kj, _, mv = precision_constants(float_type)
+    if mask is None:
+        mask = ExclusionMask(cands, offset, count, dev)
+    elif mask.offset != offset or mask.count != count:
+        raise ValueError("select_batch_kb: the mask covers another shard")
+    mask.update(evaluated_points)
+    d = _lib.KbDesc()
+    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.x_train, d.kinv, d.ld_k = x.data_ptr(), kinv.data_ptr(), kinv.shape[-1]
+    d.cand_kind, d.q = cands.kind_code, batch_size
+    d.n_cand, d.cand_offset = count, offset
+    if cands.kind == "grid":
+        for k in range(cands.dim):
+            d.grid_lo[k] = cands.lo[k]
+            d.grid_shape[k] = cands.shape[k]
+    elif cands.kind == "sobol":
+        d.cand = cands.cand_arg
+    else:                                              # explicit candidates: the shard's rows
+        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    for o in range(n_obj):
+        d.prior_var[o] = float(prior_variance[o])
+        d.length_scale[o] = float(length_scales[o])
+        d.ref_point[o] = float(ref[o])
+    d.jitter = float(kj if jitter is None else jitter)
+    d.min_variance = float(mv if min_variance is None else min_variance)
+    d.mu, d.var, d.ld = mu.ptr, var.ptr, mu.t.stride(0)
+    d.mask = mask.ptr
+    d.front, d.n_front = (front.ctypes.data if front.shape[0] else None), front.shape[0]
+    d.form = EHVI_FORMS[form]
+    tv = torch.empty(batch_size, dtype=F64, device=dev)
+    ti = torch.empty(batch_size, dtype=torch.int64, device=dev)
+    believed = torch.empty((batch_size, n_obj), dtype=F64, device=dev)
+    d.top_val, d.top_idx, d.believed = tv.data_ptr(), ti.data_ptr(), believed.data_ptr()
+    var_out = acq_last = None
+    acq_first = _Arg(acq_out, dev, write=True) if acq_out is not None else None
+    if acq_first is not None and acq_first.t.numel() != count:
+        raise ValueError(f"acq_out holds {acq_first.t.numel()} values for {count} candidates")
+    first = acq_first.t if acq_first is not None else None
+    if return_details:
+        var_out = torch.empty_like(var.t)
+        d.var_out = var_out.data_ptr()
+        acq_last = torch.empty(count, dtype=F64, device=dev)
+        d.acq_last = acq_last.data_ptr()
+        if first is None:
+            first = torch.empty(count, dtype=F64, device=dev)
+    if first is not None:
+        d.acq_first = first.data_ptr()
+    met = C_i64(0)
+    d.n_boxes_max = _C.pointer(met)
+    lib = _lib.load()
+    cap = int(box_capacity) if box_capacity is not None else max(1024, _KB_BOX_CAPACITY.get(n_obj, 0))
+    for attempt in range(4):
+        d.box_capacity = cap
+        nbytes = lib.bo_select_batch_kb_workspace_size(d)
+        hbytes = lib.bo_select_batch_kb_host_workspace_size(d)
+        if nbytes == 0 or hbytes == 0:
+            raise _lib.BoNativeError(_lib.ERR_ARG, "bo_select_batch_kb_workspace_size")
+        ws = Workspace.get(nbytes, dev)
+        hws = PinnedStaging.get(hbytes, dev)
+        d.host_ws, d.host_ws_bytes = hws.data_ptr(), hws.numel()
+        st = lib.bo_select_batch_kb(d, ws.data_ptr(), ws.numel(), stream_handle(dev))
+        if st == _lib.ERR_WORKSPACE and met.value > cap and attempt < 3:
+            cap = (2 * int(met.value) + 255) // 256 * 256   # the count that did not fit, rounded up
+            continue
+        _lib.check(st, "bo_select_batch_kb")
+        break
+    if box_capacity is None:
+        _KB_BOX_CAPACITY[n_obj] = cap
+    if acq_first is not None:
+        acq_first.finish()
+    if return_details:
+        return {"top_idx": ti, "top_val": tv, "var": var_out[:, :count], "acq_first": first, "acq_last": acq_last,
+                "believed": believed, "n_boxes_max": int(met.value)}
+    idx = ti.cpu().numpy()
+    return idx[idx >= 0].astype(np.int64)
+
+
 def update_hypervolume_improvement_exact(acquisition_values, ucb, y_vector, n_evaluations,
                                          reference_point, prior_mean, prior_variance):
     """The acquisition update of the loop (bayesian_optimization.py:195-199) as an exact HVI:

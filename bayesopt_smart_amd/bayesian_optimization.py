@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import (BATCH_STRATEGIES, ExclusionMask, ehvi_select_indices, hvi_select_indices,
-                          select_batch_bucb, select_batch_ts, select_indices, thompson_draws,
+from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, ehvi_select_indices,
+                          hvi_select_indices, select_batch_bucb, select_batch_kb, select_batch_ts,
+                          select_indices, thompson_draws,
                           update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
 
 ACQUISITIONS = ("sum_ucb", "hvi", "ehvi")
@@ -231,7 +232,10 @@ class DeviceBackend:
         takes pick s as the best candidate of posterior draw s (Thompson sampling by pathwise
         conditioning, acquisition.select_batch_ts) for "sum_ucb" and "hvi", with any number of
         ranks: the draws come from this backend's generator (ts_seed), the same on every rank, so no
-        collective is needed for them and the exchange of the top-q records merges the shards."""
+        collective is needed for them and the exchange of the top-q records merges the shards;
+        "kb" (not in the reference; "ehvi" only, one rank) takes every pick after the first from
+        the EHVI of the variance conditioned on the earlier picks over the front extended by the
+        posterior means at those picks (Kriging believer, acquisition.select_batch_kb)."""
         _check_acquisition(acquisition)
         _check_batch_strategy(batch_strategy, acquisition, batch_size, self.group)
         xd, yd, kinv = fitted
@@ -246,6 +250,18 @@ class DeviceBackend:
                                      self.cands, prior_variance, length_scales, betas, evaluated, batch_size,
                                      offset=self.offset, count=self.count, mask=self._excl_mask,
                                      float_type=self.float_type)
+        if batch_strategy == "kb":
+            predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
+                            outputs=tuple(out), topq=0, offset=self.offset, count=self.count, out=out,
+                            device=self.dev, mode=self.mode, float_type=self.float_type)
+            if self._excl_mask is None:
+                self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
+            # acq_out: the callbacks see the EHVI array "top" would show (the first pick's)
+            return select_batch_kb(self.bufs.mu_objectives, self.bufs.variance_objectives, xd, kinv, self.cands,
+                                   prior_variance, length_scales, y_evaluated, len(y_evaluated), reference_point,
+                                   evaluated, batch_size, offset=self.offset, count=self.count,
+                                   mask=self._excl_mask, float_type=self.float_type,
+                                   acq_out=self.bufs.acquisition_values)
         if batch_strategy == "ts":
             # the predict still runs (topq = 0): the callbacks' state arrays are filled
             predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
@@ -343,7 +359,9 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     (acquisition "sum_ucb" or "hvi", any number of ranks, batch_size <= BO_MAX_TOPQ), with
     `ts_features` random Fourier features and the draws of default_rng(`ts_seed`) -- every rank
     constructs the same generator, so no collective is needed for the draws (both are the
-    backend's when `backend` is given); "top", the default, is the reference's batch.
+    backend's when `backend` is given); "kb" by a Kriging believer for the EHVI (acquisition "ehvi"
+    only, one rank, batch_size <= BO_MAX_TOPQ): each pick joins the front as a believed observation
+    equal to the posterior mean; "top", the default, is the reference's batch.
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -449,9 +467,21 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
 
 
 def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
-    """What batch_strategy="bucb" / "ts" do not cover raises here, with the reason."""
-    if batch_strategy not in BATCH_STRATEGIES:
-        raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top', 'bucb' or 'ts')")
+    """What batch_strategy="bucb" / "ts" / "kb" do not cover raises here, with the reason."""
+    if batch_strategy not in ALL_BATCH_STRATEGIES:
+        raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top', 'bucb' or 'ts', "
+                         "or 'kb' with acquisition='ehvi')")
+    if batch_strategy == "kb":
+        if acquisition != "ehvi":
+            raise ValueError("batch_strategy='kb' (Kriging believer) extends the front by believed observations: "
+                             f"it is defined for acquisition='ehvi' only (got acquisition={acquisition!r})")
+        if batch_size > _lib.MAX_TOPQ:
+            raise ValueError(f"batch_strategy='kb' supports batch_size <= {_lib.MAX_TOPQ} (got {batch_size})")
+        from .distributed import collectives_on
+        if collectives_on(group):
+            raise ValueError("batch_strategy='kb' runs on one rank: with several, every pick would need an "
+                             "all-gather of the per-rank best candidates and of the believed vector")
+        return
     if batch_strategy == "ts":
         if acquisition not in ("sum_ucb", "hvi"):
             raise ValueError("batch_strategy='ts' scores posterior draws; acquisition='ehvi' integrates over "
@@ -518,7 +548,10 @@ class BayesianOptimization:
     is the best candidate of posterior draw s, acquisition.select_batch_ts, with ``ts_features``
     random Fourier features, default 1024, and the draws of numpy.random.default_rng(``ts_seed``),
     default 0 -- every rank constructs the same generator and draws anew every iteration, so the
-    ranks need no collective for the draws).
+    ranks need no collective for the draws; or "kb", with acquisition "ehvi" only: a Kriging
+    believer, every pick after the first maximises the EHVI of the variance conditioned on the
+    earlier picks over the front extended by the posterior means there,
+    acquisition.select_batch_kb).
     With several ranks, each holds its shard of the posterior arrays, the initial design is drawn
     and evaluated on rank 0 (every rank draws the same RNG numbers, so the RNG stays in step) and
     broadcast, and the loop runs as `optimize` describes.

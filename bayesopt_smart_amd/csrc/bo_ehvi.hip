@@ -22,120 +22,40 @@
 // psi is evaluated as  max(d, 0) + sigma h(|z|),  d = mu - a,  h(t) = phi(t) - t Phi(-t)
 //                      = exp(-t^2/2) (1/sqrt(2 pi) - t erfcx(t / sqrt 2) / 2):
 // phi + z Phi itself cancels for z < 0, and the linear part max(d, 0) is exact here.
+// psi, the two box walks and the rule for the form live in bo_ehvi_impl.h, which bo_kb.hip
+// includes as well.
 
-#include "bo_common.h"
-
-#include <math.h>
-#include <string.h>
+#include "bo_ehvi_impl.h"
 
 #include <algorithm>
 #include <cmath>
 #include <vector>
 
-// both kernels must round alike: no contraction but the fma written out below
-#pragma clang fp contract(off)
-
 namespace {
 
-constexpr int kEhviLdsBytes = 160 * 1024;      // LDS of a CU: one workgroup may hold all of it
-constexpr int kEhviAuto2dEdges = 40;           // auto, 2 objectives: two 256-thread tables per CU
-
-struct EhviArgs {
-  double* acq;
-  const double* mu;
-  const double* var;
-  long long ld, n;
-  const double* boxes;     // direct: [n_boxes][2 m] (bo_hvi_boxes)
-  const double* edges;     // table: the axes' edges, concatenated
-  const int* box_idx;      // table: [n_boxes][2 m] indices into the axis' edges; E_k = +inf
-  long long n_boxes;
-  int n_edges[4], edge_off[4];
-};
-
-// sigma h(t), t = |d| rs with rs = 1 / sigma.  sigma = 0 gives t = inf (or NaN at d = 0) and the
-// limit 0; h underflows to 0 well before t = 40.
-__device__ __forceinline__ double ehvi_psi(double d, double sigma, double rs) {
-  const double t = fabs(d * rs);
-  double h = 0.0;
-  if (t < 40.0) {
-    const double e = exp(-0.5 * (t * t));
-    h = e * (0.3989422804014327 - (0.5 * t) * erfcx(t * 0.7071067811865476));
-  }
-  return __builtin_fma(sigma, h, fmax(d, 0.0));
-}
-
-template <int M>
-__device__ __forceinline__ bool ehvi_load(const EhviArgs& a, long long i, bool valid, double* mu, double* sg,
-                                          double* rs) {
-  bool nan = false;
-#pragma unroll
-  for (int k = 0; k < M; ++k) {
-    mu[k] = valid ? __builtin_nontemporal_load(a.mu + (long long)k * a.ld + i) : 0.0;
-    const double v = valid ? __builtin_nontemporal_load(a.var + (long long)k * a.ld + i) : 1.0;
-    nan = nan || (mu[k] != mu[k]) || (v != v);
-    sg[k] = sqrt(fabs(v));
-    rs[k] = 1.0 / sg[k];
-  }
-  return nan;
-}
-
-// One thread per candidate, one candidate per thread: no store precedes the loads of the boxes,
-// which are then scalar loads at a wave-uniform address, in order.
+// One thread per candidate, one candidate per thread.
 template <int M>
 __global__ __launch_bounds__(256) void ehvi_direct_kernel(const EhviArgs a) {
-  const double inf = __builtin_inf();
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   const bool valid = i < a.n;
   double mu[M], sg[M], rs[M];
   const bool nan = ehvi_load<M>(a, i, valid, mu, sg, rs);
-  double h = 0.0;
-  const double* b = a.boxes;
-  for (long long t = 0; t < a.n_boxes; ++t, b += 2 * M) {
-    double v = 1.0;
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-      const double pl = ehvi_psi(mu[k] - b[k], sg[k], rs[k]);
-      const double pu = b[M + k] < inf ? ehvi_psi(mu[k] - b[M + k], sg[k], rs[k]) : 0.0;
-      if (k < M - 1) v *= pl - pu;
-      else h = __builtin_fma(v, pl - pu, h);
-    }
-  }
+  const double h = ehvi_direct_value<M>(a, mu, sg, rs);
   if (valid) bo_out_store(a.acq + i, nan ? __builtin_nan("") : h);
 }
 
 // One thread per candidate, one candidate per thread; T threads per workgroup; the table
-// [sum E][T] in dynamic LDS.  A thread reads only the column it wrote, so there is no barrier.
+// [sum E][T] in dynamic LDS.
 template <int M, int T>
 __global__ __launch_bounds__(T) void ehvi_table_kernel(const EhviArgs a) {
   extern __shared__ double ehvi_tab[];
-  double* col = ehvi_tab + threadIdx.x;
   const long long i = (long long)blockIdx.x * T + threadIdx.x;
   const bool valid = i < a.n;
   double mu[M], sg[M], rs[M];
   const bool nan = ehvi_load<M>(a, i, valid, mu, sg, rs);
-#pragma unroll
-  for (int k = 0; k < M; ++k) {
-    const double* e = a.edges + a.edge_off[k];
-    double* c = col + a.edge_off[k] * T;
-#pragma unroll 2
-    for (int j = 0; j < a.n_edges[k]; ++j) c[j * T] = ehvi_psi(mu[k] - e[j], sg[k], rs[k]);
-  }
-  double h = 0.0;
-  const int* b = a.box_idx;
-  for (long long t = 0; t < a.n_boxes; ++t, b += 2 * M) {
-    double v = 1.0;
-#pragma unroll
-    for (int k = 0; k < M; ++k) {
-      const double pl = col[(a.edge_off[k] + b[k]) * T];
-      const double pu = b[M + k] < a.n_edges[k] ? col[(a.edge_off[k] + b[M + k]) * T] : 0.0;
-      if (k < M - 1) v *= pl - pu;
-      else h = __builtin_fma(v, pl - pu, h);
-    }
-  }
+  const double h = ehvi_table_value<M, T>(a, ehvi_tab + threadIdx.x, mu, sg, rs);
   if (valid) bo_out_store(a.acq + i, nan ? __builtin_nan("") : h);
 }
-
-long long ehvi_blocks(long long n, int threads) { return (n + threads - 1) / threads; }
 
 int launch_direct(const EhviArgs& a, int m, hipStream_t s) {
   const dim3 g((unsigned)ehvi_blocks(a.n, 256));
@@ -245,21 +165,10 @@ int bo_expected_hypervolume_improvement(double* acq, const double* mu, const dou
     return BO_ERR_ARG;
   EhviArgs a;
   memset(&a, 0, sizeof(a));
-  int64_t sum_e = 0;
-  if (have_tables)
-    for (int k = 0; k < n_obj; ++k) {
-      if (n_edges[k] < 0 || (n_boxes > 0 && n_edges[k] < 1)) return BO_ERR_ARG;
-      a.n_edges[k] = n_edges[k];
-      a.edge_off[k] = (int)sum_e;
-      sum_e += n_edges[k];
-      if (sum_e > ((int64_t)1 << 20)) return BO_ERR_UNSUPPORTED;
-    }
-  const int threads = have_tables ? bo_ehvi_table_threads(sum_e) : 0;
-  if (form == 2 && threads == 0) return BO_ERR_UNSUPPORTED;
-  // auto: the rule of include/bo_amd.h (measured: profiles/ehvi_c3.jsonl)
-  const bool table = form == 2 || (form == 0 && threads != 0 && n_boxes > 0 &&
-                                   (!have_boxes || n_obj >= 3 || (n_obj == 2 && sum_e <= kEhviAuto2dEdges)));
-  if (!table && !have_boxes) return BO_ERR_UNSUPPORTED;      // auto, tables only, and they do not fit
+  int sum_e = 0, threads = 0;
+  bool table = false;
+  const int st = ehvi_plan(form, n_obj, n_boxes, have_boxes, have_tables, n_edges, &a, &sum_e, &threads, &table);
+  if (st != BO_OK) return st;
   if (n == 0) return BO_OK;
   a.acq = acq;
   a.mu = mu;

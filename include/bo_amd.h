@@ -463,6 +463,94 @@ int bo_expected_hypervolume_improvement(double* acq, const double* mu, const dou
                                         int32_t form, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Kriging-believer batches for the EHVI (Ginsbourger, Le Riche & Carraro 2010; opt-in
+ * batch_strategy "kb").  NOT in the reference.  The q best values of one EHVI array are q
+ * neighbours of one maximum; here the picks are taken one after the other, and after each one the
+ * model is conditioned on a believed observation equal to its own posterior mean at the pick.
+ * Inputs: the predict's mu_objectives / variance_objectives (`mu` / `var`, objective units,
+ * [n_obj][ld]), the fitted state (x_train, kinv), the candidates as in bo_bucb_desc, a HOST front
+ * [n_front][n_obj] and a HOST reference point, jitter and min_variance.  With front_0 = the given
+ * front and var^0 = the given variance, for t = 1..q:
+ *   boxes_t  = the decomposition bo_hvi_boxes gives for (front_{t-1}, ref_point)
+ *   acq_t[j] = the EHVI of (mu[:, j], var^(t-1)[:, j]) over boxes_t, with the bits
+ *              bo_expected_hypervolume_improvement gives for those arrays: the same psi, the same
+ *              box order and the same `form` rule, applied to boxes_t (so the form, and the table
+ *              form's workgroup size, may change from one pick to the next)
+ *   p_t      = the best candidate of acq_t in the order of bo_select_topq (NaN first, then
+ *              descending value, then ascending global index) among those neither masked nor
+ *              already picked
+ *   m_t      = mu[:, p_t], the believed observation; front_t = front_(t-1) u {m_t}.  A row with a
+ *              NaN, or not strictly above the reference point, changes no box (bo_hvi_boxes
+ *              ignores it)
+ *   var^t    = the recursion c_t, d_t, v_t of bo_bucb_desc for a pick at p_t, floored at
+ *              min_variance; unchanged for an objective whose d_t is not finite.  The mean does
+ *              not move: a believed observation equals it.
+ * When no candidate is left, top_idx[t] = -1, top_val[t] = -inf and believed[t] = NaN, and later
+ * picks likewise.  q = 1 is the top-1 of the EHVI array.  n_obj <= 4 (the box decomposition's
+ * limit), q <= BO_MAX_TOPQ, n_cand <= 2^36.  mu / var / mask / front are not modified.
+ * Deterministic: fixed-order reductions, no atomics; a workspace and a host_ws of any content give
+ * the same bits.
+ *
+ * The box decomposition runs on the HOST, so the call is host-synchronous once per pick: it reads
+ * (p_t, m_t) back, waits for that copy alone -- the variance update of pick t is already enqueued
+ * and runs meanwhile -- decomposes front_t and uploads boxes_(t+1) with their edge tables.  It is
+ * therefore NOT capturable: on a capturing stream it returns BO_ERR_UNSUPPORTED before anything is
+ * launched.  When it returns, pick q's work may still be running on the stream, but host_ws has
+ * been read for the last time and is the caller's again.  The box count of
+ * the later picks cannot be known from the descriptor: when a pick's decomposition exceeds
+ * box_capacity the call returns BO_ERR_WORKSPACE with *n_boxes_max = that count (outputs are then
+ * unspecified); the picks are deterministic, so a retry from the start with a larger capacity is
+ * correct.  The edge buffers are sized exactly: an axis has at most n_front + q + 1 edges.  form 2
+ * returns BO_ERR_UNSUPPORTED when a pick's table does not fit (bo_ehvi_table_threads).
+ * Arguments are checked before the device is touched.  Fields shared with bo_bucb_desc have its
+ * meaning. */
+typedef struct bo_kb_desc {
+  int32_t n_obj;              /* objectives (<= 4)                                            */
+  int32_t dim;                /* input dimensions (<= BO_MAX_DIM)                              */
+  int64_t n_train;            /* N >= 1                                                       */
+  const double* x_train;      /* device [n_train][dim]                                        */
+  const double* kinv;         /* device [n_obj][ld_k][ld_k]; leading N x N block = invert_k() */
+  int64_t ld_k;
+  int32_t cand_kind;          /* bo_cand_kind                                                 */
+  int32_t q;                  /* picks, 1 .. BO_MAX_TOPQ                                      */
+  const void* cand;           /* device [n_cand][dim] (kinds I64/F64); host bo_sobol_desc* (SOBOL) */
+  int64_t n_cand;             /* candidates of this call (a shard)                            */
+  int64_t cand_offset;        /* global index of this call's first candidate                  */
+  int64_t grid_lo[BO_MAX_DIM];     /* kind GRID                                              */
+  int64_t grid_shape[BO_MAX_DIM];  /* kind GRID (axis dim-1 fastest)                         */
+  double prior_var[BO_MAX_OBJ];
+  double length_scale[BO_MAX_OBJ];
+  double jitter;              /* KERNEL_JITTER added by invert_k: 1e-6 (1e-3 float32 branch)  */
+  double min_variance;        /* MIN_VARIANCE: 1e-10 (1e-6 float32 branch)                    */
+  const double* mu;           /* device [n_obj][ld]: mu_objectives (objective units)          */
+  const double* var;          /* device [n_obj][ld]: variance_objectives (already floored)    */
+  int64_t ld;                 /* row stride of mu / var / var_out (>= n_cand)                 */
+  const uint32_t* mask;       /* device, bo_excl_mask_update's layout over this shard; NULL = none */
+  const double* front;        /* HOST [n_front][n_obj] (NULL when n_front = 0)                */
+  int64_t n_front;            /* >= 0                                                         */
+  double ref_point[4];        /* HOST values, finite                                          */
+  int32_t form;               /* 0 auto, 1 direct, 2 table: bo_expected_hypervolume_improvement's */
+  int32_t reserved;
+  int64_t box_capacity;       /* >= 1: rows the device box buffers hold                       */
+  void* host_ws;              /* HOST staging, bo_select_batch_kb_host_workspace_size bytes,
+                                 8-byte aligned; pinned memory recommended (pageable memory
+                                 serialises the host step behind the variance update)         */
+  size_t host_ws_bytes;
+  double* top_val;            /* device [q]: acq_t[p_t] (-inf when no candidate is left)      */
+  int64_t* top_idx;           /* device [q]: global index of pick t, -1 = no candidate left   */
+  double* believed;           /* device [q][n_obj]: m_t                                       */
+  double* var_out;            /* optional device [n_obj][ld]: var^q                           */
+  double* acq_first;          /* optional device [n_cand]: acq_1, the plain EHVI              */
+  double* acq_last;           /* optional device [n_cand]: acq_q                              */
+  int64_t* n_boxes_max;       /* optional HOST: the largest box count met                     */
+} bo_kb_desc;
+/* bytes of device / host workspace bo_select_batch_kb needs for `desc` (0 on bad args) */
+size_t bo_select_batch_kb_workspace_size(const bo_kb_desc* desc);
+size_t bo_select_batch_kb_host_workspace_size(const bo_kb_desc* desc);
+int bo_select_batch_kb(const bo_kb_desc* desc, void* workspace, size_t workspace_bytes,
+                       void* stream);
+
+/* ------------------------------------------------------------------------------------
  * GP fit on device.
  * ---------------------------------------------------------------------------------- */
 
