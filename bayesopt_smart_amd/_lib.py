@@ -56,16 +56,21 @@ class PredictDesc(C.Structure):
     ]
 
 
+# bo_bucb_desc and bo_kb_desc open with the same fields: the fitted state, the picks, the candidates
+_UPDATE_FIELDS = [
+    ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
+    ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
+    ("cand_kind", C.c_int32), ("q", C.c_int32),
+    ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
+    ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
+    ("prior_var", C.c_double * MAX_OBJ), ("length_scale", C.c_double * MAX_OBJ),
+]
+
+
 class BucbDesc(C.Structure):
     """Mirror of bo_bucb_desc (include/bo_amd.h)."""
 
-    _fields_ = [
-        ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
-        ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
-        ("cand_kind", C.c_int32), ("q", C.c_int32),
-        ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
-        ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
-        ("prior_var", C.c_double * MAX_OBJ), ("length_scale", C.c_double * MAX_OBJ),
+    _fields_ = _UPDATE_FIELDS + [
         ("beta", C.c_double * MAX_OBJ),
         ("jitter", C.c_double), ("min_variance", C.c_double),
         ("std_mu", c_vp), ("var", c_vp), ("ld", C.c_int64), ("mask", c_vp),
@@ -76,13 +81,7 @@ class BucbDesc(C.Structure):
 class KbDesc(C.Structure):
     """Mirror of bo_kb_desc (include/bo_amd.h)."""
 
-    _fields_ = [
-        ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
-        ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
-        ("cand_kind", C.c_int32), ("q", C.c_int32),
-        ("cand", c_vp), ("n_cand", C.c_int64), ("cand_offset", C.c_int64),
-        ("grid_lo", C.c_int64 * MAX_DIM), ("grid_shape", C.c_int64 * MAX_DIM),
-        ("prior_var", C.c_double * MAX_OBJ), ("length_scale", C.c_double * MAX_OBJ),
+    _fields_ = _UPDATE_FIELDS + [
         ("jitter", C.c_double), ("min_variance", C.c_double),
         ("mu", c_vp), ("var", c_vp), ("ld", C.c_int64), ("mask", c_vp),
         ("front", c_vp), ("n_front", C.c_int64), ("ref_point", C.c_double * 4),

@@ -113,6 +113,51 @@ class ExclusionMask:
         return np.unpackbits(w.view(np.uint8), bitorder="little")[: self.count].astype(bool)
 
 
+def _shard_mask(mask, cands, offset, count, dev, evaluated_points, who):
+    """The ExclusionMask of the shard [offset, offset + count) of `cands`, updated with
+    evaluated_points: `mask` when it covers that shard (else `who` raises), a new one without."""
+    if mask is None:
+        mask = ExclusionMask(cands, offset, count, dev)
+    elif mask.offset != offset or mask.count != count:
+        raise ValueError(f"{who}: the mask covers another shard")
+    return mask.update(evaluated_points)
+
+
+def _set_cand_fields(d, cands, offset, count):
+    """The shard [offset, offset + count) of `cands` into a descriptor's candidate fields (the ones
+    bo_bucb_desc, bo_kb_desc and bo_ts_desc share)."""
+    d.dim, d.cand_kind = cands.dim, cands.kind_code
+    d.n_cand, d.cand_offset = count, offset
+    if cands.kind == "grid":
+        for k in range(cands.dim):
+            d.grid_lo[k] = cands.lo[k]
+            d.grid_shape[k] = cands.shape[k]
+    elif cands.kind == "sobol":
+        d.cand = cands.cand_arg
+    else:                                              # explicit candidates: the shard's rows
+        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+
+
+def _fitted_ok(x, kinv, dim, n_obj):
+    """x is [N, dim] and kinv [n_obj, >= N, >= N] (square)."""
+    return x.dim() == 2 and x.shape[1] == dim and kinv.dim() == 3 and kinv.shape[0] == n_obj \
+        and kinv.shape[1] == kinv.shape[2] and kinv.shape[1] >= x.shape[0]
+
+
+def _record_indices(rec, q):
+    """The valid global indices of a device record block [2 q] (values, bit-cast int64 indices)."""
+    idx = rec[q:].view(torch.int64).cpu().numpy()
+    return idx[idx >= 0]
+
+
+def _front_of(y_vector, n_evaluations, reference_point):
+    """The Pareto-efficient rows (device filter, pareto.py:12-45) of y_vector[:n_evaluations], host."""
+    from .pareto import is_pareto_efficient
+    y = y_vector[:n_evaluations]
+    front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
+    return front.cpu().numpy() if isinstance(front, torch.Tensor) else front
+
+
 def select_indices(acquisition_values, cands, evaluated_points, batch_size, dev=None, mask=None):
     """Global candidate indices of select_next_batch's choice (device top-q with exclusion).
 
@@ -228,13 +273,9 @@ def hvi_select_indices(acquisition_values, ucb, y_vector, n_evaluations, referen
     record block [2 batch_size] (values, bit-cast int64 indices) for the multi-rank exchange.
     `mask`: this shard's ExclusionMask (updated here with evaluated_points; only the new rows
     are added) -- the selection then runs bo_hvi_select_topq_masked."""
-    from .pareto import is_pareto_efficient
     if batch_size > _lib.MAX_TOPQ:
         raise ValueError(f"hvi_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
-    y = y_vector[:n_evaluations]
-    front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
-    if isinstance(front, torch.Tensor):
-        front = front.cpu().numpy()
+    front = _front_of(y_vector, n_evaluations, reference_point)
     dev = _dev_of(acquisition_values, ucb)
     u = _Arg(ucb, dev)
     acq = _Arg(acquisition_values, dev, write=True)
@@ -246,9 +287,7 @@ def hvi_select_indices(acquisition_values, ucb, y_vector, n_evaluations, referen
     shift = _host_vec(prior_mean, n_obj)
     scale = _host_vec(np.sqrt(np.asarray(prior_variance, dtype=np.float64)), n_obj)
     if mask is not None:
-        if mask.offset != offset or mask.count != n:
-            raise ValueError("hvi_select_indices: the mask covers another shard")
-        mask.update(evaluated_points)
+        _shard_mask(mask, cands, offset, n, dev, evaluated_points, "hvi_select_indices")
         _lib.check(lib.bo_hvi_select_topq_masked(acq.ptr, u.ptr, u.t.stride(0), n, n_obj, shift, scale,
                                                  boxes.data_ptr() if boxes.numel() else None, boxes.shape[0],
                                                  offset, mask.ptr, batch_size, rec.data_ptr(),
@@ -269,10 +308,7 @@ def hvi_select_indices(acquisition_values, ucb, y_vector, n_evaluations, referen
                                           rec.data_ptr(), rec.data_ptr() + 8 * batch_size, ws.data_ptr(),
                                           ws.numel(), stream_handle(dev)), "bo_hvi_select_topq")
     acq.finish()
-    if return_record:
-        return rec
-    idx = rec[batch_size:].view(torch.int64).cpu().numpy()
-    return idx[idx >= 0]
+    return rec if return_record else _record_indices(rec, batch_size)
 
 
 # ------------------------------------------------- expected hypervolume improvement (EHVI)
@@ -355,13 +391,6 @@ def expected_hypervolume_improvement(mu, var, front, reference_point, out=None, 
     return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
 
 
-def _front_of(y_vector, n_evaluations, reference_point):
-    from .pareto import is_pareto_efficient
-    y = y_vector[:n_evaluations]
-    front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
-    return front.cpu().numpy() if isinstance(front, torch.Tensor) else front
-
-
 def update_expected_hypervolume_improvement(acquisition_values, mu_objectives, variance_objectives, y_vector,
                                             n_evaluations, reference_point):
     """The acquisition update of the loop (bayesian_optimization.py:195-199) as the EHVI: the front
@@ -388,11 +417,7 @@ def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, 
     dev = _dev_of(acquisition_values, mu_objectives)
     acq = _Arg(acquisition_values, dev, write=True)
     n = acq.t.numel()
-    if mask is None:
-        mask = ExclusionMask(cands, offset, n, dev)
-    elif mask.offset != offset or mask.count != n:
-        raise ValueError("ehvi_select_indices: the mask covers another shard")
-    mask.update(evaluated_points)
+    mask = _shard_mask(mask, cands, offset, n, dev, evaluated_points, "ehvi_select_indices")
     expected_hypervolume_improvement(mu_objectives, variance_objectives,
                                      _front_of(y_vector, n_evaluations, reference_point), reference_point,
                                      out=acq.t)
@@ -403,10 +428,7 @@ def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, 
                                          rec.data_ptr() + 8 * batch_size, ws.data_ptr(), ws.numel(),
                                          stream_handle(dev)), "bo_select_topq_masked")
     acq.finish()
-    if return_record:
-        return rec
-    idx = rec[batch_size:].view(torch.int64).cpu().numpy()
-    return idx[idx >= 0]
+    return rec if return_record else _record_indices(rec, batch_size)
 
 
 BATCH_STRATEGIES = ("top", "bucb", "ts")
@@ -446,28 +468,14 @@ def select_batch_bucb(std_mu_objectives, variance_objectives, x_train, kinv, can
     x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
     kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
     n = x.shape[0]
-    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[0] != n_obj \
-            or kinv.shape[1] != kinv.shape[2] or kinv.shape[1] < n:
+    if not _fitted_ok(x, kinv, cands.dim, n_obj):
         raise ValueError("x_train must be [N, d] and kinv [n_obj, >=N, >=N]")
     kj, _, mv = precision_constants(float_type)
-    if mask is None:
-        mask = ExclusionMask(cands, offset, count, dev)
-    elif mask.offset != offset or mask.count != count:
-        raise ValueError("select_batch_bucb: the mask covers another shard")
-    mask.update(evaluated_points)
+    mask = _shard_mask(mask, cands, offset, count, dev, evaluated_points, "select_batch_bucb")
     d = _lib.BucbDesc()
-    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.n_obj, d.n_train, d.q = n_obj, n, batch_size
     d.x_train, d.kinv, d.ld_k = x.data_ptr(), kinv.data_ptr(), kinv.shape[-1]
-    d.cand_kind, d.q = cands.kind_code, batch_size
-    d.n_cand, d.cand_offset = count, offset
-    if cands.kind == "grid":
-        for k in range(cands.dim):
-            d.grid_lo[k] = cands.lo[k]
-            d.grid_shape[k] = cands.shape[k]
-    elif cands.kind == "sobol":
-        d.cand = cands.cand_arg
-    else:                                              # explicit candidates: the shard's rows
-        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    _set_cand_fields(d, cands, offset, count)
     for o in range(n_obj):
         d.prior_var[o] = float(prior_variance[o])
         d.length_scale[o] = float(length_scales[o])
@@ -568,8 +576,7 @@ def select_batch_kb(mu_objectives, variance_objectives, x_train, kinv, cands, pr
     x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
     kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
     n = x.shape[0]
-    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[0] != n_obj \
-            or kinv.shape[1] != kinv.shape[2] or kinv.shape[1] < n:
+    if not _fitted_ok(x, kinv, cands.dim, n_obj):
         raise ValueError("x_train must be [N, d] and kinv [n_obj, >=N, >=N]")
     ref = np.asarray(reference_point, dtype=np.float64).ravel()
     if ref.size != n_obj:
@@ -577,24 +584,11 @@ def select_batch_kb(mu_objectives, variance_objectives, x_train, kinv, cands, pr
     front = np.ascontiguousarray(np.asarray(_front_of(y_vector, n_evaluations, ref), dtype=np.float64)
                                  .reshape(-1, n_obj))
     kj, _, mv = precision_constants(float_type)
-    if mask is None:
-        mask = ExclusionMask(cands, offset, count, dev)
-    elif mask.offset != offset or mask.count != count:
-        raise ValueError("select_batch_kb: the mask covers another shard")
-    mask.update(evaluated_points)
+    mask = _shard_mask(mask, cands, offset, count, dev, evaluated_points, "select_batch_kb")
     d = _lib.KbDesc()
-    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.n_obj, d.n_train, d.q = n_obj, n, batch_size
     d.x_train, d.kinv, d.ld_k = x.data_ptr(), kinv.data_ptr(), kinv.shape[-1]
-    d.cand_kind, d.q = cands.kind_code, batch_size
-    d.n_cand, d.cand_offset = count, offset
-    if cands.kind == "grid":
-        for k in range(cands.dim):
-            d.grid_lo[k] = cands.lo[k]
-            d.grid_shape[k] = cands.shape[k]
-    elif cands.kind == "sobol":
-        d.cand = cands.cand_arg
-    else:                                              # explicit candidates: the shard's rows
-        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    _set_cand_fields(d, cands, offset, count)
     for o in range(n_obj):
         d.prior_var[o] = float(prior_variance[o])
         d.length_scale[o] = float(length_scales[o])
@@ -658,12 +652,7 @@ def update_hypervolume_improvement_exact(acquisition_values, ucb, y_vector, n_ev
     """The acquisition update of the loop (bayesian_optimization.py:195-199) as an exact HVI:
     the front is the Pareto-efficient subset (device filter, pareto.py:12-45) of the evaluated
     objectives y_vector[:n_evaluations]; in place into `acquisition_values`."""
-    from .pareto import is_pareto_efficient
-    y = y_vector[:n_evaluations]
-    front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
-    if isinstance(front, torch.Tensor):
-        front = front.cpu().numpy()
-    hypervolume_improvement_exact(ucb, front, reference_point, prior_mean, prior_variance,
+    hypervolume_improvement_exact(ucb, _front_of(y_vector, n_evaluations, reference_point), reference_point, prior_mean, prior_variance,
                                   out=acquisition_values)
 
 
@@ -702,8 +691,7 @@ def sample_paths(x_train, y_train, kinv, cands, prior_mean, prior_variance, leng
         y = y.contiguous()
     z, b, theta, eps = (torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64) if isinstance(a, np.ndarray) else a,
                                         dtype=F64, device=dev).contiguous() for a in draws)
-    if x.dim() != 2 or x.shape[1] != cands.dim or kinv.dim() != 3 or kinv.shape[1] != kinv.shape[2] \
-            or kinv.shape[1] < n or y.shape[0] < n or y.shape[1] < n_obj:
+    if not _fitted_ok(x, kinv, cands.dim, n_obj) or y.shape[0] < n or y.shape[1] < n_obj:
         raise ValueError("x_train must be [N, d], y_train [N, n_obj] and kinv [n_obj, >=N, >=N]")
     if theta.dim() != 3 or z.dim() != 3:
         raise ValueError("draws must be (Z [n_obj, D, d], B [n_obj, D], Theta [S, n_obj, D], E [S, n_obj, N])")
@@ -716,19 +704,11 @@ def sample_paths(x_train, y_train, kinv, cands, prior_mean, prior_variance, leng
     count = int(cands.n - offset if count is None else count)
     ld = count if ld is None else int(ld)
     d = _lib.TsDesc()
-    d.n_obj, d.dim, d.n_train = n_obj, cands.dim, n
+    d.n_obj, d.n_train = n_obj, n
     d.x_train, d.y, d.ld_y = x.data_ptr(), y.data_ptr(), y.stride(0)
     d.kinv, d.ld_k = kinv.data_ptr(), kinv.shape[-1]
-    d.cand_kind, d.n_samples, d.n_features = cands.kind_code, n_samples, n_feat
-    d.n_cand, d.cand_offset = count, offset
-    if cands.kind == "grid":
-        for k in range(cands.dim):
-            d.grid_lo[k] = cands.lo[k]
-            d.grid_shape[k] = cands.shape[k]
-    elif cands.kind == "sobol":
-        d.cand = cands.cand_arg
-    else:                                              # explicit candidates: the shard's rows
-        d.cand = cands.tensor.data_ptr() + offset * cands.dim * cands.tensor.element_size()
+    d.n_samples, d.n_features = n_samples, n_feat
+    _set_cand_fields(d, cands, offset, count)
     for o in range(n_obj):
         d.prior_mean[o] = float(prior_mean[o])
         d.prior_var[o] = float(prior_variance[o])
@@ -798,11 +778,7 @@ def select_batch_ts(x_train, y_train, kinv, cands, prior_mean, prior_variance, l
                          offset=offset, count=count, float_type=float_type, jitter=jitter)
     dev = paths.device
     n_obj = paths.shape[1]
-    if mask is None:
-        mask = ExclusionMask(cands, offset, count, dev)
-    elif mask.offset != offset or mask.count != count:
-        raise ValueError("select_batch_ts: the mask covers another shard")
-    mask.update(evaluated_points)
+    mask = _shard_mask(mask, cands, offset, count, dev, evaluated_points, "select_batch_ts")
     lib = _lib.load()
     st = stream_handle(dev)
     ws = Workspace.get(lib.bo_select_topq_workspace_size(count, batch_size), dev)
@@ -810,9 +786,8 @@ def select_batch_ts(x_train, y_train, kinv, cands, prior_mean, prior_variance, l
     # draw s's record: s + 1 values, then s + 1 bit-cast int64 indices, at doubles [s (s + 1), ...)
     rec = torch.empty(batch_size * (batch_size + 1), dtype=F64, device=dev)
     if acquisition == "hvi":
-        from .pareto import is_pareto_efficient
         yv = np.asarray(y_evaluated, dtype=np.float64)
-        front = yv[is_pareto_efficient(yv)] if len(yv) else np.zeros((0, n_obj))
+        front = _front_of(yv, len(yv), reference_point)
         boxes = torch.as_tensor(hypervolume_boxes(front, reference_point), device=dev)
         shift = _host_vec(prior_mean, n_obj)
         scale = _host_vec(np.sqrt(np.asarray(prior_variance, dtype=np.float64)), n_obj)

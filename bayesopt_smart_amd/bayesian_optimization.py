@@ -29,7 +29,7 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, ehvi_select_indices,
+from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, _record_indices, ehvi_select_indices,
                           hvi_select_indices, select_batch_bucb, select_batch_kb, select_batch_ts,
                           select_indices, thompson_draws,
                           update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
@@ -304,8 +304,7 @@ class DeviceBackend:
                                           offset=self.offset, return_record=True, mask=self._excl_mask)
             from .distributed import collectives_on, exchange_topq_rec
             if not collectives_on(self.group):
-                idx = rec[batch_size:].view(torch.int64).cpu().numpy()
-                return idx[idx >= 0]
+                return _record_indices(rec, batch_size)
             return np.asarray(exchange_topq_rec(rec, batch_size, self.group)[1], dtype=np.int64)
         if acquisition == "hvi":
             update_hypervolume_improvement_exact(self.bufs.acquisition_values, self.bufs.ucb, y_evaluated,

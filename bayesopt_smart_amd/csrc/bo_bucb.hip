@@ -30,13 +30,13 @@ extern "C" {
 
 size_t bo_select_batch_bucb_workspace_size(const bo_bucb_desc* d) {
   Layout L;
-  if (!make_layout(d, &L)) return 0;
+  if (!d || !make_layout(d, bo_cand_desc(d), &L)) return 0;
   return L.total;
 }
 
 int bo_select_batch_bucb(const bo_bucb_desc* d, void* ws, size_t ws_bytes, void* stream) {
   Layout L;
-  if (!make_layout(d, &L)) return BO_ERR_ARG;
+  if (!d || !make_layout(d, bo_cand_desc(d), &L)) return BO_ERR_ARG;
   if (!d->x_train || !d->kinv || !d->std_mu || !d->var || !d->top_val || !d->top_idx) return BO_ERR_ARG;
   if (d->cand_kind != BO_CAND_GRID && !d->cand) return BO_ERR_ARG;
   if (d->var_out == d->var || d->var_out == d->std_mu) return BO_ERR_ARG;   // the inputs stay as they are
@@ -44,7 +44,7 @@ int bo_select_batch_bucb(const bo_bucb_desc* d, void* ws, size_t ws_bytes, void*
   if (((uintptr_t)ws & 15) != 0) return BO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
   BucbArgs a;
-  const int st = fill_args(d, L, ws, &a);
+  const int st = fill_args(d, bo_cand_desc(d), L, ws, &a);
   if (st != BO_OK) return st;
   const int st0 = start_call(a, d->mask, s);
   if (st0 != BO_OK) return st0;

@@ -6,7 +6,7 @@
 // `#pragma clang fp contract(off)` holds to the end of the translation unit.
 #pragma once
 
-#include "bo_common.h"
+#include "bo_cand.h"
 
 #include <math.h>
 #include <string.h>
@@ -14,7 +14,6 @@
 namespace {
 
 constexpr int kThreads = 256;           // candidates per workgroup of the candidate pass
-constexpr int kExpTab = 256;            // 2^(j/256) table of exp2_tab
 constexpr int kChunkDoubles = 4096;     // LDS doubles of one staged chunk (rows + weights): 32 KiB
 constexpr int kMatRows = 16;            // K^-1 rows per workgroup of the mat-vec (4 per wave)
 constexpr int kMaxTrain = 65536;
@@ -22,10 +21,9 @@ constexpr int kMaxTrain = 65536;
 enum { kSelect = 1, kWriteAcq = 2 };
 
 struct BucbArgs {
-  int n_obj, dim, dimp, n, q, cand_kind, idx32, ldu;   // ldu = n + q: row stride of u
-  long long n_cand, cand_offset, ld, ld_k;
-  long long grid_lo[BO_MAX_DIM], grid_shape[BO_MAX_DIM];
-  const void* cand;
+  int n_obj, dimp, n, q, ldu;       // ldu = n + q: row stride of u
+  long long ld, ld_k;
+  CandArgs cand;                    // the shard; its points are centred on training row 0
   const double* x_train;
   const double* kinv;
   const double* std_mu;
@@ -48,74 +46,14 @@ struct BucbArgs {
   double* acq_out;
   double* top_val;
   long long* top_idx;
-  SobolArgs sob;
 };
-
-// 2^t with the 2^(j/256) table in LDS: the predict's generation (bo_predict_impl.h exp2_tab;
-// |relative error| < 4e-17 from the polynomial, very negative -> exactly 0).
-__device__ __forceinline__ double exp2_tab(double t, const double* tb) {
-  const double x = fmax(t, -1075.0);
-  const double s = __builtin_fma(x, 256.0, 6755399441055744.0);
-  const int ki = (int)__double_as_longlong(s);
-  const double kd = s - 6755399441055744.0;
-  const double r = __builtin_fma(kd, -0.00390625, x);
-  double p = __builtin_fma(9.6181291076284772e-03, r, 5.5504108664821580e-02);
-  p = __builtin_fma(p, r, 2.4022650695910071e-01);
-  p = __builtin_fma(p, r, 6.9314718055994531e-01);
-  p = __builtin_fma(p, r, 1.0);
-  return __builtin_ldexp(p * tb[ki & (kExpTab - 1)], ki >> 8);
-}
-
-// coordinate k (< dim) of local candidate j, minus training row 0's (the centre): differences of
-// centred coordinates keep full precision for point sets far from the origin
-__device__ __forceinline__ double cand_coord(const BucbArgs& a, long long j, int k) {
-  if (a.cand_kind == BO_CAND_I64) return (double)((const long long*)a.cand)[j * a.dim + k] - a.x_train[k];
-  if (a.cand_kind == BO_CAND_SOBOL)
-    return bo_sobol_coord(a.sob, k, (unsigned long long)(a.cand_offset + j)) - a.x_train[k];
-  return ((const double*)a.cand)[j * a.dim + k] - a.x_train[k];
-}
-
-template <int DIMP>
-__device__ __forceinline__ void load_centred(const BucbArgs& a, long long j, double (&c)[DIMP]) {
-#pragma unroll
-  for (int k = 0; k < DIMP; ++k) c[k] = 0.0;
-  if (a.cand_kind == BO_CAND_GRID) {
-    if (a.idx32) {                       // 32-bit divisions (the 64-bit ones are ~10x longer)
-      unsigned int gi = (unsigned int)(a.cand_offset + j);
-#pragma unroll
-      for (int k = DIMP - 1; k >= 0; --k) {
-        if (k < a.dim) {
-          const unsigned int n = (unsigned int)a.grid_shape[k];
-          const unsigned int qq = gi / n;
-          c[k] = (double)(a.grid_lo[k] + (long long)(gi - qq * n)) - a.x_train[k];
-          gi = qq;
-        }
-      }
-      return;
-    }
-    long long gi = a.cand_offset + j;
-#pragma unroll
-    for (int k = DIMP - 1; k >= 0; --k) {
-      if (k < a.dim) {
-        const long long n = a.grid_shape[k];
-        const long long qq = gi / n;
-        c[k] = (double)(a.grid_lo[k] + (gi - qq * n)) - a.x_train[k];
-        gi = qq;
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < DIMP; ++k)
-    if (k < a.dim) c[k] = cand_coord(a, j, k);
-}
 
 // xc[f][k] = x_train[f][k] - x_train[0][k] (padded coordinates 0)
 __global__ __launch_bounds__(256) void bucb_prep_kernel(BucbArgs a) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long long)a.n * a.dimp) return;
   const int f = (int)(i / a.dimp), k = (int)(i - (long long)f * a.dimp);
-  a.xc[i] = k < a.dim ? a.x_train[(long long)f * a.dim + k] - a.x_train[k] : 0.0;
+  a.xc[i] = k < a.cand.dim ? a.x_train[(long long)f * a.cand.dim + k] - a.x_train[k] : 0.0;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -133,7 +71,7 @@ __global__ __launch_bounds__(kThreads) void bucb_cand_kernel(BucbArgs a, int t, 
   __shared__ TopEntry s_red[kThreads / 64];
   const int tid = threadIdx.x;
   const long long j = (long long)blockIdx.x * kThreads + tid;
-  const bool valid = j < a.n_cand;
+  const bool valid = j < a.cand.n_cand;
   double acc[NOB];
 #pragma unroll
   for (int o = 0; o < NOB; ++o) acc[o] = 0.0;
@@ -143,7 +81,7 @@ __global__ __launch_bounds__(kThreads) void bucb_cand_kernel(BucbArgs a, int t, 
     double c[DIMP];
 #pragma unroll
     for (int k = 0; k < DIMP; ++k) c[k] = 0.0;
-    if (valid) load_centred<DIMP>(a, j, c);
+    if (valid) bo_cand_load<DIMP, true>(a.cand, a.x_train, j, c);
     double nl2[NOB], lpv[NOB];
 #pragma unroll
     for (int o = 0; o < NOB; ++o) {
@@ -203,7 +141,7 @@ __global__ __launch_bounds__(kThreads) void bucb_cand_kernel(BucbArgs a, int t, 
   if (flags & kSelect) {
     if (valid && (flags & kWriteAcq) && a.acq_out) a.acq_out[j] = acq;
     long long gi = -1;
-    if (valid && !((a.mask[j >> 5] >> (j & 31)) & 1u)) gi = a.cand_offset + j;
+    if (valid && !((a.mask[j >> 5] >> (j & 31)) & 1u)) gi = a.cand.cand_offset + j;
     const TopEntry b = bo_block_best(acq, gi, s_red);
     if (tid == 0) a.partial[blockIdx.x] = b;
   }
@@ -225,8 +163,8 @@ __global__ __launch_bounds__(1024) void bucb_pick_kernel(BucbArgs a, int t, long
     if (bo_better(e.v, e.i, bv, bi)) { bv = e.v; bi = e.i; }
   }
   const TopEntry w = bo_block_best(bv, bi, s_red);
-  long long p = w.i >= 0 ? w.i - a.cand_offset : -1;
-  if (p >= a.n_cand) p = -1;                       // cannot happen: entries come from this shard
+  long long p = w.i >= 0 ? w.i - a.cand.cand_offset : -1;
+  if (p >= a.cand.n_cand) p = -1;                       // cannot happen: entries come from this shard
   if (tid == 0) {
     a.top_val[t] = p >= 0 ? w.v : -__builtin_inf();
     a.top_idx[t] = p >= 0 ? w.i : -1;
@@ -236,7 +174,7 @@ __global__ __launch_bounds__(1024) void bucb_pick_kernel(BucbArgs a, int t, long
   if (!gen) return;
   if (tid == 0) {
     double c[BO_MAX_DIM];
-    if (p >= 0) load_centred<BO_MAX_DIM>(a, p, c);
+    if (p >= 0) bo_cand_load<BO_MAX_DIM, true>(a.cand, a.x_train, p, c);
     for (int k = 0; k < BO_MAX_DIM; ++k) s_c[k] = p >= 0 ? c[k] : 0.0;
     for (int k = 0; k < a.dimp; ++k) a.pc[(long long)t * a.dimp + k] = s_c[k];
   }
@@ -368,27 +306,15 @@ struct Layout {
 
 size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
-bool make_layout(const bo_bucb_desc* d, Layout* L) {
-  if (!d) return false;
-  if (d->n_obj < 1 || d->n_obj > BO_MAX_OBJ || d->dim < 1 || d->dim > BO_MAX_DIM) return false;
+// d: the update's fields; c: the candidates (bo_cand_desc of the caller's own descriptor, which
+// for bo_kb.hip is not `d`: d's candidate fields and d->dim are not read)
+bool make_layout(const bo_bucb_desc* d, const CandDesc& c, Layout* L) {
+  if (d->n_obj < 1 || d->n_obj > BO_MAX_OBJ || c.dim < 1 || c.dim > BO_MAX_DIM) return false;
   if (d->n_train < 1 || d->n_train > kMaxTrain || d->ld_k < d->n_train) return false;
   if (d->q < 1 || d->q > BO_MAX_TOPQ) return false;
-  if (d->n_cand < 1 || d->n_cand > (1LL << 38) || d->cand_offset < 0 || d->cand_offset > (1LL << 62) ||
-      d->ld < d->n_cand)
+  if (c.count < 1 || c.count > (1LL << 38) || c.offset < 0 || c.offset > (1LL << 62) || d->ld < c.count)
     return false;
-  if (d->cand_kind < BO_CAND_I64 || d->cand_kind > BO_CAND_SOBOL) return false;
-  if (d->cand_kind == BO_CAND_GRID) {
-    unsigned long long total = 1;
-    for (int k = 0; k < d->dim; ++k) {
-      const long long lim = 1LL << 53;                       // every coordinate exact in f64
-      if (d->grid_shape[k] <= 0 || d->grid_lo[k] <= -lim || d->grid_lo[k] >= lim ||
-          d->grid_shape[k] >= lim - d->grid_lo[k])
-        return false;
-      if (total > (1ull << 62) / (unsigned long long)d->grid_shape[k]) return false;
-      total *= (unsigned long long)d->grid_shape[k];
-    }
-    if ((unsigned long long)d->cand_offset + (unsigned long long)d->n_cand > total) return false;
-  }
+  if (!bo_cand_check(c)) return false;
   for (int o = 0; o < d->n_obj; ++o) {
     if (!(d->prior_var[o] > 0.0) || !(d->prior_var[o] < __builtin_inf())) return false;
     if (!(d->length_scale[o] * d->length_scale[o] > 0.0)) return false;
@@ -396,8 +322,8 @@ bool make_layout(const bo_bucb_desc* d, Layout* L) {
   }
   if (!(d->jitter >= 0.0) || !(d->jitter < __builtin_inf()) || !(d->min_variance >= 0.0)) return false;
   const size_t n = (size_t)d->n_train, q = (size_t)d->q, no = (size_t)d->n_obj;
-  L->dimp = (d->dim + 1) & ~1;
-  L->blocks = (d->n_cand + kThreads - 1) / kThreads;
+  L->dimp = (c.dim + 1) & ~1;
+  L->blocks = (c.count + kThreads - 1) / kThreads;
   size_t off = 0;
   auto take = [&](size_t bytes) { const size_t at = off; off += align256(bytes); return at; };
   L->xc = take(n * L->dimp * 8);
@@ -410,44 +336,27 @@ bool make_layout(const bo_bucb_desc* d, Layout* L) {
   L->u = take(no * (n + q) * 8);
   L->ok = take(no * 4);
   L->pick = take(q * 8);
-  L->mask = take(bo_excl_mask_bytes(d->n_cand));
+  L->mask = take(bo_excl_mask_bytes(c.count));
   L->partial = take((size_t)L->blocks * sizeof(TopEntry));
   L->var = d->var_out ? off : take(no * (size_t)d->ld * 8);   // the running variance
   L->total = off;
   return true;
 }
 
-// The kernels' argument block of `d` over the workspace `ws` laid out by L (host only; nothing is
-// launched).  BO_OK, or the status of a bad Sobol descriptor.
-int fill_args(const bo_bucb_desc* d, const Layout& L, void* ws, BucbArgs* out) {
+// The kernels' argument block of (d, c) over the workspace `ws` laid out by L (host only; nothing
+// is launched).  BO_OK, or the status of a bad Sobol descriptor.
+int fill_args(const bo_bucb_desc* d, const CandDesc& c, const Layout& L, void* ws, BucbArgs* out) {
   BucbArgs& a = *out;
   memset(&a, 0, sizeof(a));
+  const int st = bo_cand_fill(&a.cand, c);
+  if (st != BO_OK) return st;
   a.n_obj = d->n_obj;
-  a.dim = d->dim;
   a.dimp = L.dimp;
   a.n = (int)d->n_train;
   a.q = d->q;
-  a.cand_kind = d->cand_kind;
   a.ldu = a.n + a.q;
-  a.n_cand = d->n_cand;
-  a.cand_offset = d->cand_offset;
   a.ld = d->ld;
   a.ld_k = d->ld_k;
-  a.cand = d->cand;
-  for (int k = 0; k < BO_MAX_DIM; ++k) a.grid_shape[k] = 1;
-  if (d->cand_kind == BO_CAND_GRID) {
-    a.cand = nullptr;
-    a.idx32 = d->cand_offset + d->n_cand < (1LL << 31) ? 1 : 0;
-    for (int k = 0; k < d->dim; ++k) {
-      a.grid_lo[k] = d->grid_lo[k];
-      a.grid_shape[k] = d->grid_shape[k];
-      if (d->grid_shape[k] >= (1LL << 31)) a.idx32 = 0;
-    }
-  } else if (d->cand_kind == BO_CAND_SOBOL) {
-    const int st = bo_sobol_fill(&a.sob, d->dim, (const bo_sobol_desc*)d->cand);
-    if (st != BO_OK) return st;
-    a.cand = nullptr;
-  }
   a.x_train = d->x_train;
   a.kinv = d->kinv;
   a.std_mu = d->std_mu;
@@ -484,7 +393,7 @@ int fill_args(const bo_bucb_desc* d, const Layout& L, void* ws, BucbArgs* out) {
 // the call's own mask: the caller's bits (its words over this shard), then the picks; and the
 // centred training rows
 int start_call(const BucbArgs& a, const uint32_t* mask, hipStream_t s) {
-  const size_t mask_words = ((size_t)a.n_cand + 31) / 32;
+  const size_t mask_words = ((size_t)a.cand.n_cand + 31) / 32;
   if (mask)
     BO_CHECK_HIP(hipMemcpyAsync(a.mask, mask, mask_words * 4, hipMemcpyDeviceToDevice, s));
   else

@@ -277,6 +277,26 @@ inline unsigned int bo_hash_slots(long long n) {
 // host -- streaming stores, so that they do not evict the L2-resident W stream.
 __device__ __forceinline__ void bo_out_store(double* p, double v) { __builtin_nontemporal_store(v, p); }
 
+// 2^t for the K* exponents (t <= a few tens; -inf / very negative -> exactly 0), with the
+// 2^(j/256) table `tb` (kExpTab entries) in LDS: t = n + j/256 + r, |r| <= 1/512; 2^r by its
+// degree-4 Taylor polynomial in r ln 2 (|term 5| < 4e-17 relative).  The round-to-nearest
+// k = 256 t comes from the 1.5 * 2^52 shifter, whose low 32 bits hold k in two's complement
+// (j = k & 255, n = k >> 8).  10 f64 operations (the libm-style exp costs ~20).  The one kernel
+// value of the predict, the hallucinated-observation update and the posterior draws.
+constexpr int kExpTab = 256;
+__device__ __forceinline__ double exp2_tab(double t, const double* tb) {
+  const double x = fmax(t, -1075.0);
+  const double s = __builtin_fma(x, 256.0, 6755399441055744.0);
+  const int ki = (int)__double_as_longlong(s);
+  const double kd = s - 6755399441055744.0;
+  const double r = __builtin_fma(kd, -0.00390625, x);
+  double p = __builtin_fma(9.6181291076284772e-03, r, 5.5504108664821580e-02);
+  p = __builtin_fma(p, r, 2.4022650695910071e-01);
+  p = __builtin_fma(p, r, 6.9314718055994531e-01);
+  p = __builtin_fma(p, r, 1.0);
+  return __builtin_ldexp(p * tb[ki & (kExpTab - 1)], ki >> 8);
+}
+
 // Workgroup-wide best entry (selection order) of one entry per thread; every thread gets it.
 // `red` is a __shared__ scratch of blockDim.x / 64 entries.
 __device__ __forceinline__ TopEntry bo_block_best(double v, long long i, TopEntry* red) {

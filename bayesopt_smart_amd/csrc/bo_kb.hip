@@ -161,24 +161,16 @@ struct KbLayout {
   int64_t edge_cap;
 };
 
-bo_bucb_desc as_bucb(const bo_kb_desc* d) {
+// the update's fields of `d` (bo_bucb_impl.h takes the candidates as bo_cand_desc(d))
+bo_bucb_desc update_desc(const bo_kb_desc* d) {
   bo_bucb_desc b;
   memset(&b, 0, sizeof(b));
   b.n_obj = d->n_obj;
-  b.dim = d->dim;
   b.n_train = d->n_train;
   b.x_train = d->x_train;
   b.kinv = d->kinv;
   b.ld_k = d->ld_k;
-  b.cand_kind = d->cand_kind;
   b.q = d->q;
-  b.cand = d->cand;
-  b.n_cand = d->n_cand;
-  b.cand_offset = d->cand_offset;
-  for (int k = 0; k < BO_MAX_DIM; ++k) {
-    b.grid_lo[k] = d->grid_lo[k];
-    b.grid_shape[k] = d->grid_shape[k];
-  }
   for (int o = 0; o < BO_MAX_OBJ; ++o) {
     b.prior_var[o] = d->prior_var[o];
     b.length_scale[o] = d->length_scale[o];
@@ -202,8 +194,8 @@ bool make_kb_layout(const bo_kb_desc* d, KbLayout* L) {
     return false;
   for (int k = 0; k < d->n_obj; ++k)
     if (!(d->ref_point[k] - d->ref_point[k] == 0.0)) return false;          // NaN or infinite
-  const bo_bucb_desc b = as_bucb(d);
-  if (!make_layout(&b, &L->b)) return false;
+  const bo_bucb_desc b = update_desc(d);
+  if (!make_layout(&b, bo_cand_desc(d), &L->b)) return false;
   const size_t m = (size_t)d->n_obj, cap = (size_t)d->box_capacity;
   L->edge_cap = (int64_t)m * (d->n_front + d->q + 1);
   L->tab_bytes = align256(cap * 2 * m * 8 + (size_t)L->edge_cap * 8 + cap * 2 * m * 4);
@@ -257,9 +249,9 @@ int bo_select_batch_kb(const bo_kb_desc* d, void* ws, size_t ws_bytes, void* str
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(s, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return BO_ERR_UNSUPPORTED;
   }
-  const bo_bucb_desc bd = as_bucb(d);
+  const bo_bucb_desc bd = update_desc(d);
   BucbArgs a;
-  const int st_args = fill_args(&bd, L.b, ws, &a);
+  const int st_args = fill_args(&bd, bo_cand_desc(d), L.b, ws, &a);
   if (st_args != BO_OK) return st_args;
   const int m = d->n_obj, q = d->q;
   char* base = (char*)ws;

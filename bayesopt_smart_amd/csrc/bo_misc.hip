@@ -1,5 +1,6 @@
-// ABI housekeeping (status strings, device count) and the host side of the Sobol candidates.
-#include "bo_common.h"
+// ABI housekeeping (status strings, device count) and the host side of the candidates: the Sobol
+// direction numbers, the checks and the packing of a shard's description (bo_cand.h).
+#include "bo_cand.h"
 
 #include <string.h>
 
@@ -41,6 +42,44 @@ int bo_sobol_fill(SobolArgs* s, int dim, const bo_sobol_desc* d) {
     for (int j = 0; j < bits; ++j) s->v[k][j] = (unsigned int)(v[j] << (bits - 1 - j));
     s->lo[k] = d->lo[k];
     s->scale[k] = d->scale[k];
+  }
+  return BO_OK;
+}
+
+bool bo_cand_check(const CandDesc& d) {
+  if (d.kind < BO_CAND_I64 || d.kind > BO_CAND_SOBOL) return false;
+  if (d.kind != BO_CAND_GRID) return true;
+  unsigned long long total = 1;
+  for (int k = 0; k < d.dim; ++k) {
+    const long long lim = 1LL << 53;                       // every coordinate exact in f64
+    if (d.grid_shape[k] <= 0 || d.grid_lo[k] <= -lim || d.grid_lo[k] >= lim ||
+        d.grid_shape[k] >= lim - d.grid_lo[k])
+      return false;
+    if (total > (1ull << 62) / (unsigned long long)d.grid_shape[k]) return false;
+    total *= (unsigned long long)d.grid_shape[k];
+  }
+  return (unsigned long long)d.offset + (unsigned long long)d.count <= total;
+}
+
+int bo_cand_fill(CandArgs* a, const CandDesc& d) {
+  memset(a, 0, sizeof(*a));
+  a->kind = d.kind;
+  a->dim = d.dim;
+  a->n_cand = d.count;
+  a->cand_offset = d.offset;
+  a->rows = d.cand;
+  for (int k = 0; k < BO_MAX_DIM; ++k) a->grid_shape[k] = 1;
+  if (d.kind == BO_CAND_GRID) {
+    a->rows = nullptr;
+    a->idx32 = d.offset >= 0 && d.offset + d.count < (1LL << 31) ? 1 : 0;
+    for (int k = 0; k < d.dim; ++k) {
+      a->grid_lo[k] = d.grid_lo[k];
+      a->grid_shape[k] = d.grid_shape[k];
+      if (d.grid_shape[k] >= (1LL << 31)) a->idx32 = 0;
+    }
+  } else if (d.kind == BO_CAND_SOBOL) {
+    a->rows = nullptr;
+    return bo_sobol_fill(&a->sob, d.dim, (const bo_sobol_desc*)d.cand);
   }
   return BO_OK;
 }

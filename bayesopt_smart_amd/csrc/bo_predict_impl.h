@@ -28,7 +28,7 @@ constexpr int kPanelSteps = 128;        // k-steps of 4 training rows per regist
 constexpr int kPF = 4;                  // W prefetch ring depth (pairs of k-steps)
 constexpr int kCMaxEp = 16;             // E-pairs (32 rows each) whose accumulators one wave holds
 constexpr int kC32MaxEp = 16;           // E-quads (64 rows each) per group of the f32 kernel
-constexpr int kExpTab = 256;            // 2^(j/256) table of exp2_tab
+using ::kExpTab;                        // 2^(j/256) table of exp2_tab (bo_common.h)
 
 struct FusedArgs {
   int n_obj, dim, n_train, n_pad;       // n_pad = padded training rows (multiple of 32 / 64)
@@ -352,6 +352,7 @@ using bo::kCMaxEp;
 using bo::kC32MaxEp;
 using bo::kExpTab;
 
+// the decode of bo_cand.h's bo_cand_load<DIM, false>, kept here for this kernel's register budget
 template <int DIM>
 __device__ __forceinline__ void load_candidate(const FusedArgs& a, long long j, bool valid,
                                                double (&c)[DIM]) {
@@ -466,24 +467,6 @@ __device__ __forceinline__ void prime_ring(__amdgpu_buffer_rsrc_t wr, int voff, 
     wa[p] = wload(wr, voff, base + (p << 11));
     wb[p] = wload(wr, voff, base + (p << 11) + 1024);
   }
-}
-
-// 2^t for the K* exponents (t <= a few tens; -inf / very negative -> exactly 0), with the
-// 2^(j/256) table `tb` in LDS: t = n + j/256 + r, |r| <= 1/512; 2^r by its degree-4 Taylor
-// polynomial in r ln 2 (|term 5| < 4e-17 relative).  The round-to-nearest k = 256 t comes from
-// the 1.5 * 2^52 shifter, whose low 32 bits hold k in two's complement (j = k & 255, n = k >> 8).
-// 10 f64 operations (the libm-style exp costs ~20).
-__device__ __forceinline__ double exp2_tab(double t, const double* tb) {
-  const double x = fmax(t, -1075.0);
-  const double s = __builtin_fma(x, 256.0, 6755399441055744.0);
-  const int ki = (int)__double_as_longlong(s);
-  const double kd = s - 6755399441055744.0;
-  const double r = __builtin_fma(kd, -0.00390625, x);
-  double p = __builtin_fma(9.6181291076284772e-03, r, 5.5504108664821580e-02);
-  p = __builtin_fma(p, r, 2.4022650695910071e-01);
-  p = __builtin_fma(p, r, 6.9314718055994531e-01);
-  p = __builtin_fma(p, r, 1.0);
-  return __builtin_ldexp(p * tb[ki & (kExpTab - 1)], ki >> 8);
 }
 
 

@@ -6,7 +6,7 @@
 //   bo_pareto_mask         pareto.py:12-45
 // These are HBM-bound integer/compare/elementwise kernels: coalesced, one pass.
 
-#include "bo_common.h"
+#include "bo_cand.h"
 
 #include <math.h>
 #include <string.h>
@@ -101,10 +101,8 @@ __global__ void hvi_kernel(double* __restrict__ acq, const double* __restrict__ 
 // ------------------------------------------------------------------------ selection
 struct SelArgs {
   const double* acq;
-  long long n_cand, cand_offset;
-  int kind, dim, n_excl, topq;
-  const void* cand;
-  long long grid_lo[BO_MAX_DIM], grid_shape[BO_MAX_DIM];
+  CandArgs cand;            // decoded only where candidates are compared with points (n_excl > 0)
+  int n_excl, topq;
   const double* excl;
   // open-addressing hash set of the evaluated points (keys: bo_point_key, 0 = empty; idx: the
   // point's row): built per workgroup in LDS (lds_slots > 0), else in the
@@ -115,8 +113,6 @@ struct SelArgs {
   unsigned int hmask;
   TopEntry* partial;
   long long partial_cap;    // entries of `partial` (the debug build checks every write)
-  int idx32;                // grid: every global index below 2^31 (32-bit decode)
-  SobolArgs sob;            // kind BO_CAND_SOBOL
   // candidate exclusion mask (bo_excl_mask_update): bit j of word j / 32 set = local candidate j
   // equals an evaluated point.  When given, an excluded element is dropped as it is loaded (key
   // 0, as an out-of-range one) and n_excl is 0: no hash, no probes.
@@ -136,57 +132,21 @@ __global__ void excl_hash_kernel(unsigned long long* __restrict__ keys, int* __r
   if (key != 0ull) bo_hash_insert(keys, idx, mask, key, e);
 }
 
-__device__ __forceinline__ double cand_coord(const SelArgs& a, long long j, int k);
-
 // candidate j equal (every coordinate) to an evaluated point?  Hash probe when a table is
 // given, else the O(n_excl) scan.
 __device__ __forceinline__ bool cand_excluded(const SelArgs& a, long long j,
                                               const unsigned long long* hk, const int* hi,
                                               unsigned int hm) {
   double c[BO_MAX_DIM];
-  if (a.kind == BO_CAND_GRID && a.idx32) {   // 32-bit divisions (the 64-bit ones are ~10x longer)
-    unsigned int gi = (unsigned int)(a.cand_offset + j);
-#pragma unroll
-    for (int k = BO_MAX_DIM - 1; k >= 0; --k) {
-      c[k] = 0.0;
-      if (k < a.dim) {
-        const unsigned int n = (unsigned int)a.grid_shape[k];
-        const unsigned int q = gi / n;
-        c[k] = (double)(a.grid_lo[k] + (long long)(gi - q * n));
-        gi = q;
-      }
-    }
-  } else if (a.kind == BO_CAND_GRID) {   // all coordinates from one chain of divisions
-    long long gi = a.cand_offset + j;
-#pragma unroll
-    for (int k = BO_MAX_DIM - 1; k >= 0; --k) {
-      c[k] = 0.0;
-      if (k < a.dim) {
-        c[k] = (double)(a.grid_lo[k] + gi % a.grid_shape[k]);
-        gi /= a.grid_shape[k];
-      }
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < BO_MAX_DIM; ++k) c[k] = k < a.dim ? cand_coord(a, j, k) : 0.0;
-  }
-  if (hk) return bo_hash_contains(hk, hi, hm, a.excl, a.dim, c, a.dim, a.n_excl);
+  bo_cand_load<BO_MAX_DIM, false>(a.cand, nullptr, j, c);
+  if (hk) return bo_hash_contains(hk, hi, hm, a.excl, a.cand.dim, c, a.cand.dim, a.n_excl);
   for (int e = 0; e < a.n_excl; ++e) {
     bool eq = true;
 #pragma unroll
-    for (int k = 0; k < BO_MAX_DIM; ++k) eq = eq && (k >= a.dim || a.excl[(long long)e * a.dim + k] == c[k]);
+    for (int k = 0; k < BO_MAX_DIM; ++k) eq = eq && (k >= a.cand.dim || a.excl[(long long)e * a.cand.dim + k] == c[k]);
     if (eq) return true;
   }
   return false;
-}
-
-__device__ __forceinline__ double cand_coord(const SelArgs& a, long long j, int k) {
-  if (a.kind == BO_CAND_I64) return (double)((const long long*)a.cand)[j * a.dim + k];
-  if (a.kind == BO_CAND_F64) return ((const double*)a.cand)[j * a.dim + k];
-  if (a.kind == BO_CAND_SOBOL) return bo_sobol_coord(a.sob, k, (unsigned long long)(a.cand_offset + j));
-  long long gi = a.cand_offset + j;
-  for (int t = a.dim - 1; t > k; --t) gi /= a.grid_shape[t];
-  return (double)(a.grid_lo[k] + gi % a.grid_shape[k]);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -199,17 +159,17 @@ __device__ __forceinline__ double cand_coord(const SelArgs& a, long long j, int 
 __global__ void excl_mask_grid_kernel(unsigned int* __restrict__ bits, SelArgs a, int first) {
   const int e = first + blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= a.n_excl) return;
-  const double* p = a.excl + (long long)e * a.dim;
+  const double* p = a.excl + (long long)e * a.cand.dim;
   long long gi = 0;
-  for (int k = 0; k < a.dim; ++k) {
+  for (int k = 0; k < a.cand.dim; ++k) {
     const double x = p[k];
-    const double lo = (double)a.grid_lo[k];
+    const double lo = (double)a.cand.grid_lo[k];
     // NaN or outside [lo, lo + shape) or not an integer: no candidate equals it
-    if (!(x >= lo && x < lo + (double)a.grid_shape[k]) || x != __builtin_floor(x)) return;
-    gi = gi * a.grid_shape[k] + ((long long)x - a.grid_lo[k]);
+    if (!(x >= lo && x < lo + (double)a.cand.grid_shape[k]) || x != __builtin_floor(x)) return;
+    gi = gi * a.cand.grid_shape[k] + ((long long)x - a.cand.grid_lo[k]);
   }
-  const long long j = gi - a.cand_offset;
-  if (j < 0 || j >= a.n_cand) return;
+  const long long j = gi - a.cand.cand_offset;
+  if (j < 0 || j >= a.cand.n_cand) return;
   atomicOr(bits + (j >> 5), 1u << (j & 31));
 }
 
@@ -219,7 +179,7 @@ __global__ void excl_mask_scan_kernel(unsigned int* __restrict__ bits, SelArgs a
                                       const unsigned long long* __restrict__ hk,
                                       const int* __restrict__ hi, unsigned int hm) {
   const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;   // blockDim 256
-  const bool hit = j < a.n_cand && cand_excluded(a, j, hk, hi, hm);
+  const bool hit = j < a.cand.n_cand && cand_excluded(a, j, hk, hi, hm);
   const unsigned long long b = __ballot(hit);
   if ((threadIdx.x & 63) == 0 && b) {
     const long long w = j >> 5;                  // j is a multiple of 64 in lane 0
@@ -324,7 +284,7 @@ struct SelExcl {
   const int* hi;
   unsigned int hm;
   __device__ bool operator()(long long gi) const {
-    return a->n_excl > 0 && cand_excluded(*a, gi - a->cand_offset, hk, hi, hm);
+    return a->n_excl > 0 && cand_excluded(*a, gi - a->cand.cand_offset, hk, hi, hm);
   }
 };
 
@@ -640,10 +600,10 @@ __global__ __launch_bounds__(1024) void select_small_kernel(SelArgs a, HviIn h) 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long long j = s0 + wave * wspan + 64 * u + lane;
-        const bool in = j < a.n_cand;
+        const bool in = j < a.cand.n_cand;
         const double v = in ? __builtin_nontemporal_load(a.acq + j) : 0.0;
         const bool ok = in && !xbit(a.xbits, j);
-        dst.i[u] = ok ? a.cand_offset + j : -1;
+        dst.i[u] = ok ? a.cand.cand_offset + j : -1;
         dst.k[u] = ok ? bo_order_key(v, 0) : 0ull;
       }
     } else {
@@ -655,7 +615,7 @@ __global__ __launch_bounds__(1024) void select_small_kernel(SelArgs a, HviIn h) 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long long j = s0 + wave * wspan + 64 * u + lane;
-        const bool in = j < a.n_cand;
+        const bool in = j < a.cand.n_cand;
         nan[u] = false;
         hv[u] = 0.0;
 #pragma unroll
@@ -684,26 +644,26 @@ __global__ __launch_bounds__(1024) void select_small_kernel(SelArgs a, HviIn h) 
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const long long j = s0 + wave * wspan + 64 * u + lane;
-        const bool in = j < a.n_cand;
+        const bool in = j < a.cand.n_cand;
         const double v = nan[u] ? __builtin_nan("") : hv[u];
         if (in) __builtin_nontemporal_store(v, h.acq_out + j);      // streamed: read by nothing here
         const bool ok = in && !xbit(a.xbits, j);
-        dst.i[u] = ok ? a.cand_offset + j : -1;
+        dst.i[u] = ok ? a.cand.cand_offset + j : -1;
         dst.k[u] = ok ? bo_order_key(v, 0) : 0ull;
       }
     }
   };
   // the first span's loads go out before the hash build (they need no table)
-  if (b_first < a.n_cand) load_span(b_first, run);
+  if (b_first < a.cand.n_cand) load_span(b_first, run);
   if (a.n_excl == 0) {
     // lean form: nothing to probe (the exclusion mask dropped the evaluated points at load, or
     // there are none); a lane keeps the best U of all its spans, then the rounds
-    if (b_first >= a.n_cand) {
+    if (b_first >= a.cand.n_cand) {
 #pragma unroll
       for (int u = 0; u < U; ++u) { run.k[u] = 0ull; run.i[u] = -1; }
     }
     run.sort();
-    for (long long s0 = b_first + b_stride; s0 < a.n_cand; s0 += b_stride) {   // workgroup-uniform
+    for (long long s0 = b_first + b_stride; s0 < a.cand.n_cand; s0 += b_stride) {   // workgroup-uniform
       LaneRun<U> nx;
       load_span(s0, nx);
       nx.sort();
@@ -730,7 +690,7 @@ __global__ __launch_bounds__(1024) void select_small_kernel(SelArgs a, HviIn h) 
     for (int t = tid; t < a.lds_slots; t += blockDim.x) lkeys[t] = 0ull;
     __syncthreads();
     for (int e = tid; e < a.n_excl; e += blockDim.x) {
-      const unsigned long long key = bo_point_key(a.excl + (long long)e * a.dim, a.dim);
+      const unsigned long long key = bo_point_key(a.excl + (long long)e * a.cand.dim, a.cand.dim);
       if (key != 0ull) bo_hash_insert(lkeys, lidx, (unsigned int)a.lds_slots - 1, key, e);
     }
     if (!BO_IN(a.n_excl, a.lds_slots / 2 + 1, "LDS hash load")) return;
@@ -743,7 +703,7 @@ __global__ __launch_bounds__(1024) void select_small_kernel(SelArgs a, HviIn h) 
   const SelExcl ex{&a, hk, hi, hm};
   double lv = -__builtin_inf();
   long long li = -1;
-  for (long long s0 = b_first; s0 < a.n_cand; s0 += b_stride) {     // workgroup-uniform
+  for (long long s0 = b_first; s0 < a.cand.n_cand; s0 += b_stride) {     // workgroup-uniform
     if (s0 != b_first) load_span(s0, run);
 #ifdef BO_SEL_TIMING
     __builtin_amdgcn_s_waitcnt(0);
@@ -845,7 +805,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long long j = b_first + u * stride + lane;
-      pre[u] = j < a.n_cand ? __builtin_nontemporal_load(a.acq + j) : 0.0;
+      pre[u] = j < a.cand.n_cand ? __builtin_nontemporal_load(a.acq + j) : 0.0;
     }
   }
   if (a.lds_slots > 0) {
@@ -853,7 +813,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
     for (int t = tid; t < a.lds_slots; t += blockDim.x) lkeys[t] = 0ull;
     __syncthreads();
     for (int e = tid; e < a.n_excl; e += blockDim.x) {
-      const unsigned long long key = bo_point_key(a.excl + (long long)e * a.dim, a.dim);
+      const unsigned long long key = bo_point_key(a.excl + (long long)e * a.cand.dim, a.cand.dim);
       if (key != 0ull) bo_hash_insert(lkeys, lidx, (unsigned int)a.lds_slots - 1, key, e);
     }
     if (!BO_IN(a.n_excl, a.lds_slots / 2 + 1, "LDS hash load")) return;
@@ -866,14 +826,14 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
   long long li = -1, ti = -1;
   const unsigned long long below = (1ull << lane) - 1ull;
   // wave-uniform trip count: every lane stays in the loop for the ballots and broadcasts
-  for (long long b0 = b_first; b0 < a.n_cand; b0 += U * stride) {
+  for (long long b0 = b_first; b0 < a.cand.n_cand; b0 += U * stride) {
     double val[U];
     bool live[U];                     // in range and not masked out (xbits)
     bool any = false;
 #pragma unroll
     for (int u = 0; u < U; ++u) {     // all U loads in flight before any element is looked at
       const long long j = b0 + u * stride + lane;
-      const bool in = j < a.n_cand;
+      const bool in = j < a.cand.n_cand;
       live[u] = in && !xbit(a.xbits, j);
       if constexpr (M == 0) {
         val[u] = b0 == b_first ? pre[u] : (in ? __builtin_nontemporal_load(a.acq + j) : 0.0);
@@ -907,7 +867,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const long long j = b0 + u * stride + lane;
-      pend[u] = live[u] && bo_better(val[u], a.cand_offset + j, tv, ti);
+      pend[u] = live[u] && bo_better(val[u], a.cand.cand_offset + j, tv, ti);
     }
     for (;;) {
       int cnt = 0;
@@ -921,7 +881,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
         long long mi = -1;
 #pragma unroll
         for (int u = 0; u < U; ++u) {
-          const long long gi = a.cand_offset + b0 + u * stride + lane;
+          const long long gi = a.cand.cand_offset + b0 + u * stride + lane;
           const unsigned long long k = pend[u] ? bo_order_key(val[u], gi) : 0ull;
           const bool b = bo_key_before(k, gi, mk, mi);
           mk = b ? k : mk;
@@ -936,7 +896,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
       int off[U], total = 0;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const long long gi = a.cand_offset + b0 + u * stride + lane;
+        const long long gi = a.cand.cand_offset + b0 + u * stride + lane;
         take[u] = pend[u] && !bo_better(bv, bix, val[u], gi);
         const unsigned long long bb = __ballot(take[u]);
         off[u] = total + __popcll(bb & below);
@@ -949,15 +909,15 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
         for (int u = 0; u < U; ++u)
           if (take[u] && off[u] >= c0 && off[u] < c0 + 64 && BO_IN(off[u] - c0, 64, "chunk buf[off - c0]")) {
             buf[off[u] - c0].v = val[u];
-            buf[off[u] - c0].i = a.cand_offset + b0 + u * stride + lane;
+            buf[off[u] - c0].i = a.cand.cand_offset + b0 + u * stride + lane;
           }
         wave_lds_sync();
         bool p = lane < total - c0;
         const double nv = p ? buf[lane].v : -__builtin_inf();
         const long long ni = p ? buf[lane].i : -1;
         p = p && bo_better(nv, ni, tv, ti);
-        if (a.n_excl > 0 && p && BO_IN(ni - a.cand_offset, a.n_cand, "chunk candidate"))
-          p = !cand_excluded(a, ni - a.cand_offset, hk, hi, hm);
+        if (a.n_excl > 0 && p && BO_IN(ni - a.cand.cand_offset, a.cand.n_cand, "chunk candidate"))
+          p = !cand_excluded(a, ni - a.cand.cand_offset, hk, hi, hm);
         if (__ballot(p) == 0ull) continue;
         if (bo_readlane_i(li, 0) < 0 && __popcll(__ballot(p)) > 24) {
           // empty list and a large chunk: the sorted chunk's head is the list (rank insertion
@@ -976,7 +936,7 @@ __global__ __launch_bounds__(256) void select_stream_kernel(SelArgs a, HviIn h) 
       // what the bound held back stays pending only while it still beats T
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const long long gi = a.cand_offset + b0 + u * stride + lane;
+        const long long gi = a.cand.cand_offset + b0 + u * stride + lane;
         pend[u] = pend[u] && !take[u] && bo_better(val[u], gi, tv, ti);
       }
     }
@@ -1170,6 +1130,15 @@ size_t bo_select_topq_workspace_size(int64_t n_cand, int32_t topq) {
 
 namespace {
 
+// The selection's own grid rule -- any positive shape; bo_cand_check's limits are the batch
+// strategies' -- then the packing.
+int sel_cand_fill(CandArgs* a, const CandDesc& d) {
+  if (d.kind == BO_CAND_GRID)
+    for (int k = 0; k < d.dim; ++k)
+      if (d.grid_shape[k] <= 0) return BO_ERR_ARG;
+  return bo_cand_fill(a, d);
+}
+
 // select_next_batch over an acquisition array (m == 0) or over the exact HVI computed from the
 // UCB arrays in the same pass (m >= 1, `h`), written into h->acq_out first.
 int select_impl(const double* acq, int64_t n_cand, int32_t kind, const void* cand,
@@ -1196,31 +1165,12 @@ int select_impl(const double* acq, int64_t n_cand, int32_t kind, const void* can
   if (!ws || ws_bytes < bo_select_topq_workspace_size(n_cand, topq)) return BO_ERR_WORKSPACE;
   SelArgs a;
   memset(&a, 0, sizeof(a));
+  const int st_cand = sel_cand_fill(&a.cand, CandDesc{kind, cand, grid_lo, grid_shape, dim, cand_offset, n_cand});
+  if (st_cand != BO_OK) return st_cand;
   a.xbits = xbits;
   a.acq = acq;
-  a.n_cand = n_cand;
-  a.cand_offset = cand_offset;
-  a.kind = kind;
-  a.dim = dim;
   a.n_excl = (int)n_excl;
   a.topq = topq;
-  a.cand = cand;
-  if (kind == BO_CAND_SOBOL) {            // `cand` is a host bo_sobol_desc*
-    const int st = bo_sobol_fill(&a.sob, dim, (const bo_sobol_desc*)cand);
-    if (st != BO_OK) return st;
-    a.cand = nullptr;
-  }
-  for (int k = 0; k < BO_MAX_DIM; ++k) a.grid_shape[k] = 1;
-  if (kind == BO_CAND_GRID) {
-    for (int k = 0; k < dim; ++k) {
-      if (grid_shape[k] <= 0) return BO_ERR_ARG;
-      a.grid_lo[k] = grid_lo[k];
-      a.grid_shape[k] = grid_shape[k];
-    }
-    a.idx32 = cand_offset >= 0 && cand_offset + n_cand < (1LL << 31) ? 1 : 0;
-    for (int k = 0; k < dim; ++k)
-      if (grid_shape[k] >= (1LL << 31)) a.idx32 = 0;
-  }
   a.excl = excl;
   a.partial = (TopEntry*)ws;
   a.partial_cap = (long long)(sel_lists_bytes(topq) / sizeof(TopEntry));
@@ -1355,34 +1305,21 @@ int bo_excl_mask_update(uint32_t* mask, int64_t n_cand, int32_t kind, const void
   if (n_excl == first_excl || n_cand == 0) return BO_OK;
   SelArgs a;
   memset(&a, 0, sizeof(a));
-  a.n_cand = n_cand;
-  a.cand_offset = cand_offset;
-  a.kind = kind;
-  a.dim = dim;
+  const int st_cand = sel_cand_fill(&a.cand, CandDesc{kind, cand, grid_lo, grid_shape, dim, cand_offset, n_cand});
+  if (st_cand != BO_OK) return st_cand;
   a.n_excl = (int)n_excl;
-  a.cand = cand;
   a.excl = excl;
-  for (int k = 0; k < BO_MAX_DIM; ++k) a.grid_shape[k] = 1;
+  // the inverse map (point -> index) holds where every grid coordinate is exact in f64 and the
+  // index cannot overflow; any other grid goes through the candidate scan
   bool arith = kind == BO_CAND_GRID;
-  if (kind == BO_CAND_SOBOL) {
-    const int st = bo_sobol_fill(&a.sob, dim, (const bo_sobol_desc*)cand);
-    if (st != BO_OK) return st;
-    a.cand = nullptr;
-  }
-  if (kind == BO_CAND_GRID) {
+  if (arith) {
     unsigned long long total = 1;
     for (int k = 0; k < dim; ++k) {
-      if (grid_shape[k] <= 0) return BO_ERR_ARG;
-      a.grid_lo[k] = grid_lo[k];
-      a.grid_shape[k] = grid_shape[k];
-      const long long lim = 1LL << 53;          // every grid coordinate exact in f64
+      const long long lim = 1LL << 53;
       if (grid_lo[k] <= -lim || grid_lo[k] >= lim || grid_shape[k] >= lim - grid_lo[k]) arith = false;
       total = total * (unsigned long long)grid_shape[k];
       if (total >= (1ull << 62)) arith = false;
     }
-    a.idx32 = cand_offset >= 0 && cand_offset + n_cand < (1LL << 31) ? 1 : 0;
-    for (int k = 0; k < dim; ++k)
-      if (grid_shape[k] >= (1LL << 31)) a.idx32 = 0;
   }
   const int first = (int)first_excl, cnt = (int)(n_excl - first_excl);
   if (arith) {

@@ -20,7 +20,7 @@
 // An output element is one accumulator element of one wave: its own chain over the rows in row
 // order, with the row chunks cut at the same rows for every candidate -- so the value of a
 // candidate does not depend on the workgroup, the tile position or the shard it is computed in.
-#include "bo_common.h"
+#include "bo_cand.h"
 
 #include <math.h>
 #include <string.h>
@@ -30,7 +30,6 @@ namespace {
 constexpr int kThreads = 256;           // 4 waves
 constexpr int kTiles = 2;               // 16-candidate tiles per wave: 128 candidates per workgroup
 constexpr int kCandPerBlock = (kThreads / 64) * 16 * kTiles;
-constexpr int kExpTab = 256;            // 2^(j/256) table of exp2_tab
 constexpr int kChunkDoubles = 4096;     // LDS doubles of one staged chunk (rows + weights): 32 KiB
 constexpr int kMatRows = 16;            // K^-1 rows per workgroup of the mat-vec (4 per wave)
 constexpr int kMatSamples = 4;          // right-hand sides per pass over a K^-1 row
@@ -38,10 +37,9 @@ constexpr int kMaxTrain = 65536;
 constexpr int kMaxFeatures = 65536;     // BO_TS_MAX_FEATURES
 
 struct TsArgs {
-  int n_obj, dim, dimp, n, np, nf, fp, ns, sp, cand_kind, idx32;   // np / fp: rows padded to 4; sp: samples to 16
-  long long n_cand, cand_offset, ld, ld_k, ld_y;
-  long long grid_lo[BO_MAX_DIM], grid_shape[BO_MAX_DIM];
-  const void* cand;
+  int n_obj, dimp, n, np, nf, fp, ns, sp;   // np / fp: rows padded to 4; sp: samples to 16
+  long long ld, ld_k, ld_y;
+  CandArgs cand;         // the points of this pass (centred on training row 0): the training rows, then the shard
   const double* x_train;
   const double* y;
   const double* kinv;
@@ -57,65 +55,7 @@ struct TsArgs {
   double* gx;            // [ns][n_obj][n]        g(X), then r
   double* out;           // [ns][n_obj][ld]
   double* weights_out;   // [ns][n_obj][n] or null
-  SobolArgs sob;
 };
-
-// 2^t with the 2^(j/256) table in LDS: the predict's generation (bo_predict_impl.h exp2_tab)
-__device__ __forceinline__ double exp2_tab(double t, const double* tb) {
-  const double x = fmax(t, -1075.0);
-  const double s = __builtin_fma(x, 256.0, 6755399441055744.0);
-  const int ki = (int)__double_as_longlong(s);
-  const double kd = s - 6755399441055744.0;
-  const double r = __builtin_fma(kd, -0.00390625, x);
-  double p = __builtin_fma(9.6181291076284772e-03, r, 5.5504108664821580e-02);
-  p = __builtin_fma(p, r, 2.4022650695910071e-01);
-  p = __builtin_fma(p, r, 6.9314718055994531e-01);
-  p = __builtin_fma(p, r, 1.0);
-  return __builtin_ldexp(p * tb[ki & (kExpTab - 1)], ki >> 8);
-}
-
-// coordinate k (< dim) of local candidate j, minus training row 0's (bo_bucb.hip's decoding)
-__device__ __forceinline__ double cand_coord(const TsArgs& a, long long j, int k) {
-  if (a.cand_kind == BO_CAND_I64) return (double)((const long long*)a.cand)[j * a.dim + k] - a.x_train[k];
-  if (a.cand_kind == BO_CAND_SOBOL)
-    return bo_sobol_coord(a.sob, k, (unsigned long long)(a.cand_offset + j)) - a.x_train[k];
-  return ((const double*)a.cand)[j * a.dim + k] - a.x_train[k];
-}
-
-template <int DIMP>
-__device__ __forceinline__ void load_centred(const TsArgs& a, long long j, double (&c)[DIMP]) {
-#pragma unroll
-  for (int k = 0; k < DIMP; ++k) c[k] = 0.0;
-  if (a.cand_kind == BO_CAND_GRID) {
-    if (a.idx32) {
-      unsigned int gi = (unsigned int)(a.cand_offset + j);
-#pragma unroll
-      for (int k = DIMP - 1; k >= 0; --k) {
-        if (k < a.dim) {
-          const unsigned int n = (unsigned int)a.grid_shape[k];
-          const unsigned int qq = gi / n;
-          c[k] = (double)(a.grid_lo[k] + (long long)(gi - qq * n)) - a.x_train[k];
-          gi = qq;
-        }
-      }
-      return;
-    }
-    long long gi = a.cand_offset + j;
-#pragma unroll
-    for (int k = DIMP - 1; k >= 0; --k) {
-      if (k < a.dim) {
-        const long long n = a.grid_shape[k];
-        const long long qq = gi / n;
-        c[k] = (double)(a.grid_lo[k] + (gi - qq * n)) - a.x_train[k];
-        gi = qq;
-      }
-    }
-    return;
-  }
-#pragma unroll
-  for (int k = 0; k < DIMP; ++k)
-    if (k < a.dim) c[k] = cand_coord(a, j, k);
-}
 
 // Rows and weights in the staged layouts.  Padded rows (to multiples of 4) and padded samples
 // (to multiples of 16) have weight 0 and generate finite values (cos(0), pv): they add exact zeros.
@@ -129,7 +69,7 @@ __global__ __launch_bounds__(256) void ts_prep_kernel(TsArgs a) {
        i += (long long)gridDim.x * blockDim.x) {
     if (i < n_xr) {
       const int f = (int)(i / rs), k = (int)(i - (long long)f * rs);
-      a.xr[i] = (f < a.n && k < a.dim) ? a.x_train[(long long)f * a.dim + k] - a.x_train[k] : 0.0;
+      a.xr[i] = (f < a.n && k < a.cand.dim) ? a.x_train[(long long)f * a.cand.dim + k] - a.x_train[k] : 0.0;
     } else if (i < n_xr + n_fr) {
       const long long l = i - n_xr;
       const int k = (int)(l % rs);
@@ -138,7 +78,7 @@ __global__ __launch_bounds__(256) void ts_prep_kernel(TsArgs a) {
       double v = 0.0;
       if (f < a.nf) {
         const long long zf = (long long)o * a.nf + f;
-        if (k < a.dim) v = (a.z[zf * a.dim + k] / a.ls[o]) * inv_2pi;
+        if (k < a.cand.dim) v = (a.z[zf * a.cand.dim + k] / a.ls[o]) * inv_2pi;
         else if (k == a.dimp) v = a.phase[zf] * inv_2pi;
       }
       a.fr[l] = v;
@@ -185,7 +125,7 @@ __global__ __launch_bounds__(kThreads) void ts_paths_kernel(TsArgs a, int prior_
     const long long j = jw + 16 * t + cl;
 #pragma unroll
     for (int k = 0; k < DIMP; ++k) c[t][k] = 0.0;
-    if (j < a.n_cand) load_centred<DIMP>(a, j, c[t]);
+    if (j < a.cand.n_cand) bo_cand_load<DIMP, true>(a.cand, a.x_train, j, c[t]);
   }
   d4 acc[kTiles][ST];
 #pragma unroll
@@ -260,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void ts_paths_kernel(TsArgs a, int prior_
 #pragma unroll
       for (int reg = 0; reg < 4; ++reg) {
         const long long j = jw + 16 * t + kq + 4 * reg;
-        if (s < a.ns && j < a.n_cand) {
+        if (s < a.ns && j < a.cand.n_cand) {
           const double f = acc[t][st][reg];                   // f - pm
           bo_out_store(a.out + ((long long)s * a.n_obj + o) * a.ld + j, prior_only ? f : f / spv);
         }
@@ -324,7 +264,7 @@ __global__ __launch_bounds__(256) void ts_matvec_kernel(TsArgs a) {
 
 template <int DIMP>
 hipError_t launch_paths(const TsArgs& a, int prior_only, hipStream_t s) {
-  const dim3 grid((unsigned)((a.n_cand + kCandPerBlock - 1) / kCandPerBlock), (unsigned)a.n_obj);
+  const dim3 grid((unsigned)((a.cand.n_cand + kCandPerBlock - 1) / kCandPerBlock), (unsigned)a.n_obj);
   switch (a.sp / 16) {
     case 1: hipLaunchKernelGGL((ts_paths_kernel<DIMP, 1>), grid, dim3(kThreads), 0, s, a, prior_only); break;
     case 2: hipLaunchKernelGGL((ts_paths_kernel<DIMP, 2>), grid, dim3(kThreads), 0, s, a, prior_only); break;
@@ -361,19 +301,7 @@ bool make_layout(const bo_ts_desc* d, Layout* L) {
   if (d->n_cand < 1 || d->n_cand > (1LL << 36) || d->cand_offset < 0 || d->cand_offset > (1LL << 62) ||
       d->ld < d->n_cand)
     return false;
-  if (d->cand_kind < BO_CAND_I64 || d->cand_kind > BO_CAND_SOBOL) return false;
-  if (d->cand_kind == BO_CAND_GRID) {
-    unsigned long long total = 1;
-    for (int k = 0; k < d->dim; ++k) {
-      const long long lim = 1LL << 53;                       // every coordinate exact in f64
-      if (d->grid_shape[k] <= 0 || d->grid_lo[k] <= -lim || d->grid_lo[k] >= lim ||
-          d->grid_shape[k] >= lim - d->grid_lo[k])
-        return false;
-      if (total > (1ull << 62) / (unsigned long long)d->grid_shape[k]) return false;
-      total *= (unsigned long long)d->grid_shape[k];
-    }
-    if ((unsigned long long)d->cand_offset + (unsigned long long)d->n_cand > total) return false;
-  }
+  if (!bo_cand_check(bo_cand_desc(d))) return false;
   for (int o = 0; o < d->n_obj; ++o) {
     if (!(d->prior_var[o] > 0.0) || !(d->prior_var[o] < __builtin_inf())) return false;
     if (!(d->length_scale[o] * d->length_scale[o] > 0.0)) return false;
@@ -414,14 +342,15 @@ int bo_sample_paths(const bo_ts_desc* d, void* ws, size_t ws_bytes, void* stream
   if (!ws || ws_bytes < L.total) return BO_ERR_WORKSPACE;
   if (((uintptr_t)ws & 15) != 0) return BO_ERR_ARG;
   hipStream_t s = (hipStream_t)stream;
+  // the two point sets of the path kernel: the training rows as explicit candidates (g(X)), and
+  // the caller's shard -- a bad Sobol descriptor fails here, before the first launch
+  CandArgs train, shard;
+  (void)bo_cand_fill(&train, CandDesc{BO_CAND_F64, d->x_train, nullptr, nullptr, d->dim, 0, d->n_train});
+  const int st_shard = bo_cand_fill(&shard, bo_cand_desc(d));
+  if (st_shard != BO_OK) return st_shard;
   TsArgs a;
   memset(&a, 0, sizeof(a));
-  if (d->cand_kind == BO_CAND_SOBOL) {                       // checked before the first launch
-    const int st = bo_sobol_fill(&a.sob, d->dim, (const bo_sobol_desc*)d->cand);
-    if (st != BO_OK) return st;
-  }
   a.n_obj = d->n_obj;
-  a.dim = d->dim;
   a.dimp = L.dimp;
   a.n = (int)d->n_train;
   a.np = L.np;
@@ -438,7 +367,7 @@ int bo_sample_paths(const bo_ts_desc* d, void* ws, size_t ws_bytes, void* stream
   a.phase = d->phase;
   a.theta = d->theta;
   a.eps = d->eps;
-  for (int k = 0; k < BO_MAX_DIM; ++k) a.grid_shape[k] = 1;
+  a.cand = train;
   for (int o = 0; o < d->n_obj; ++o) {
     const double ls = d->length_scale[o];
     a.nl2[o] = -0.5 / (ls * ls) * 1.4426950408889634;        // the predict's exponent, base 2
@@ -463,11 +392,7 @@ int bo_sample_paths(const bo_ts_desc* d, void* ws, size_t ws_bytes, void* stream
   hipLaunchKernelGGL(ts_prep_kernel, dim3((unsigned)prep_blocks), dim3(256), 0, s, a);
   BO_CHECK_HIP(hipGetLastError());
 
-  // g(X): the prior part over the training rows as explicit candidates
-  a.cand_kind = BO_CAND_F64;
-  a.cand = d->x_train;
-  a.n_cand = d->n_train;
-  a.cand_offset = 0;
+  // g(X): the prior part over the training rows
   a.ld = d->n_train;
   a.out = a.gx;
   BO_CHECK_HIP(launch_paths_dim(a, 1, s));
@@ -481,23 +406,9 @@ int bo_sample_paths(const bo_ts_desc* d, void* ws, size_t ws_bytes, void* stream
   BO_CHECK_HIP(hipGetLastError());
 
   // the candidates
-  a.cand_kind = d->cand_kind;
-  a.cand = d->cand;
-  a.n_cand = d->n_cand;
-  a.cand_offset = d->cand_offset;
+  a.cand = shard;
   a.ld = d->ld;
   a.out = d->paths;
-  if (d->cand_kind == BO_CAND_GRID) {
-    a.cand = nullptr;
-    a.idx32 = d->cand_offset + d->n_cand < (1LL << 31) ? 1 : 0;
-    for (int k = 0; k < d->dim; ++k) {
-      a.grid_lo[k] = d->grid_lo[k];
-      a.grid_shape[k] = d->grid_shape[k];
-      if (d->grid_shape[k] >= (1LL << 31)) a.idx32 = 0;
-    }
-  } else if (d->cand_kind == BO_CAND_SOBOL) {
-    a.cand = nullptr;
-  }
   BO_CHECK_HIP(launch_paths_dim(a, 0, s));
   return BO_OK;
 }
