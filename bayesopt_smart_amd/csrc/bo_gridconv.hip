@@ -71,7 +71,9 @@ struct AccLds {          // doubles: tabE[2][2R]; then ints, to a whole double: 
       : ints(4 * R), part(kClassLists + 1),
         bytes((size_t)ints * sizeof(double) + (size_t)(part + kConvAccWaves + 1) / 2 * 2 * sizeof(int)) {}
 };
-struct ContractLds {     // doubles: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] (ints, one double); then ints: cn[NP]
+struct ContractLds {     // doubles: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2] (ints, one double); then ints: cn[NP],
+                         // a training point's column in the low 16 bits and its row above them (both < 2^15);
+                         // the doubles are the workspace's image of an objective's tables (conv_ctab_doubles)
   int HB, tabH, hband, cn;
   size_t bytes;          // the tables, or the `lists` top-q entries that the waves of a workgroup merge from offset 0
                          // once the tables are done with (more than the tables only on a grid of a few columns)
@@ -83,8 +85,9 @@ struct ContractLds {     // doubles: tabB[2][HB] | tabH[Cpad + C - 1] | hband[2]
 };
 
 // ---------------------------------------------------------------------------------------
-// Pair list.  blockIdx.x < tau_blocks: the lists of kListWaves values of tau; the blocks after
-// them: Tm for every objective.
+// Pair list.  blockIdx.x < tau_blocks: the lists of kListWaves values of tau; the tm_blocks after
+// them: Tm for every objective; the blocks after those: the exp tables of the two kernels behind
+// this one, once per call and distinct length scale (conv_tables).
 //
 // One tau is one WAVE's: the pairs (n <= m, c_n + c_m = tau) in (n ascending, m in bucket order)
 // order -- lane l owns a contiguous range of n, counts its pairs (the partner bucket is column
@@ -122,13 +125,71 @@ __device__ __forceinline__ void conv_list_done(const ConvArgs& a, int tau, int k
   }
 }
 
-__global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvArgs a, int tau_blocks, int dyn) {
+// The tables of the accumulate kernel (tabE, described above) and of the contraction (tabB, tabH and the bands,
+// described there), written to the workspace by thread t0 of nthr: they depend on (l_o, R, C) alone, so the
+// objective that is the first with its length scale builds them and every workgroup behind copies them.
+// Contraction entries below kTabFlush become +0.0 (a NaN entry compares false and stays); a band is the
+// largest |t| that the same comparison kept, raised from the setup block's zero by one integer atomicMax per
+// wave (integer maxima: no order in them).
+__device__ __forceinline__ void conv_tables(const ConvArgs& a, int t0, int nthr, int lane) {
+  const int R2 = 2 * a.R;
+  const ContractLds L(a.C, a.Cpad, a.LT, a.NP);
+  for (int o = 0; o < a.n_obj; ++o) {
+    if (a.tix[o] != o) continue;
+    const double nhl = a.nhl[o];
+    double* tabE = a.tabE + (size_t)o * 2 * R2;
+    for (int t = t0; t < 2 * R2; t += nthr) {
+      const int par = t >= R2 ? 1 : 0, h = t - par * R2;
+      const double m = (double)(2 * h + par - (R2 - 2));
+      tabE[t] = exp(0.5 * nhl * (m * m));
+    }
+    double* tabB = a.ctab + (size_t)o * conv_ctab_doubles(a.C, a.Cpad, a.LT);
+    double* tabH = tabB + L.tabH;
+    int mq = 0;
+    int mm = 0;
+    for (int t = t0; t < 2 * L.HB; t += nthr) {
+      const int par = t >= L.HB ? 1 : 0, h = t - par * L.HB;
+      const int mi = 2 * h + par - (a.LT - 1);
+      const double m = (double)mi;
+      const double v = exp(0.5 * nhl * (m * m));
+      const bool flush = v < kTabFlush;
+      tabB[t] = flush ? 0.0 : v;
+      if (!flush) mq = max(mq, abs(mi));
+    }
+    for (int t = t0; t < a.Cpad + a.C - 1; t += nthr) {
+      const int mi = t - (a.C - 1);
+      const double m = (double)mi;
+      const double v = exp(nhl * (m * m));
+      const bool flush = v < kTabFlush;
+      tabH[t] = flush ? 0.0 : v;
+      if (!flush) mm = max(mm, abs(mi));
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+      mq = max(mq, __shfl_xor(mq, d, 64));
+      mm = max(mm, __shfl_xor(mm, d, 64));
+    }
+    if (lane == 0) {
+      int* hband = (int*)(tabB + L.hband);
+      atomicMax(hband, mq);
+      atomicMax(hband + 1, mm);
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * kListWaves) void conv_list_kernel(const ConvArgs a, int tau_blocks, int tm_blocks,
+                                                                    int dyn) {
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   const int tid = threadIdx.x;
+  if ((int)blockIdx.x >= tau_blocks + tm_blocks) {
+    conv_tables(a, (blockIdx.x - tau_blocks - tm_blocks) * (64 * kListWaves) + tid,
+                (gridDim.x - tau_blocks - tm_blocks) * (64 * kListWaves), tid & 63);
+    return;
+  }
   if ((int)blockIdx.x >= tau_blocks) {
     // Tm[o][s][i] = pv alpha_n H(i - r_n), n = order[s]; rows s >= N are zero
     const long long total = (long long)a.NP * a.ldr;
-    const long long stride = (long long)(gridDim.x - tau_blocks) * (64 * kListWaves);
+    const long long stride = (long long)tm_blocks * (64 * kListWaves);
     for (int o = 0; o < a.n_obj; ++o) {
       const double nhl = a.nhl[o], pv = a.pv[o];
       double* tm = a.Tm + (size_t)o * a.NP * a.ldr;
@@ -357,17 +418,14 @@ __global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
   if (__builtin_amdgcn_readfirstlane(*a.flag) != 0) return;
   extern __shared__ __attribute__((aligned(16))) double sd[];
   const int tid = threadIdx.x, lane = tid & 63, o = blockIdx.y;
-  const double nhl = a.nhl[o];
   const int R2 = 2 * a.R;
   const AccLds L(a.R);
   double* tabE = sd;
   int* cst = (int*)(sd + L.ints);                     // first position of each class list
   int* part = cst + L.part;
-  for (int t = tid; t < 2 * R2; t += 64 * kConvAccWaves) {
-    const int par = t >= R2 ? 1 : 0, h = t - par * R2;
-    const double m = (double)(2 * h + par - (R2 - 2));
-    tabE[t] = exp(0.5 * nhl * (m * m));
-  }
+  // the list kernel's table of this objective's length scale, 16 bytes per load
+  const double2* te = (const double2*)(a.tabE + (size_t)a.tix[o] * 2 * R2);
+  for (int t = tid; t < R2; t += 64 * kConvAccWaves) ((double2*)tabE)[t] = te[t];
   if (dyn) {
     // the class lists one after the other, the longest class first (the shards of a class in turn):
     // list j is class kConvClasses - 1 - j / kConvShards, shard j % kConvShards; an exclusive scan of their
@@ -450,7 +508,8 @@ __global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
 //                (split by parity: consecutive columns read consecutive doubles);
 //      mean      H(j - c_n)  = tabH[j - c_n + C - 1]; the rows of Tm and cn[] are the training points
 //                in column-bucketed order (`order`), so the points near a tile are consecutive rows.
-// The tables tabB, tabH and hband (ContractLds) are rebuilt when the length scale changes.
+// The tables tabB, tabH and hband (ContractLds) are the list kernel's (conv_tables), copied from the workspace
+// when the objective's table index changes.
 // Bands: table entries below kTabFlush are stored as +0.0, and hband holds the largest |t| of an entry
 // that the same comparison kept (hq for E, hm for H).  A tile of columns j0 .. j0 + TW - 1 runs
 //   variance  the k-blocks that hold a tau of [2 j0 - hq, 2 (j0 + TW - 1) + hq],
@@ -460,9 +519,9 @@ __global__ __launch_bounds__(64 * kConvAccWaves) void conv_acc_kernel(
 // The k-blocks ascend for every tile alike; the accumulators are read behind mfma_fence.
 // Selection: a wave keeps a top-q list over its tiles; at the end the waves of a workgroup merge theirs in LDS
 // and the workgroup writes one list, so the grid is bounded by the lists the final merge reads (n_lists), not
-// by the waves.  BO_BUILD_VARIANT=CT_NOOUT / CT_NOSEL / CT_NOTAB / CT_BCONST / CT_ACONST are timing-only builds
-// without the output stores, the selection, the table build, the B operand's LDS reads or the A operand's loads
-// (DESIGN.md §9.6 item 6).
+// by the waves.  BO_BUILD_VARIANT=CT_NOOUT / CT_NOSEL / CT_BCONST / CT_ACONST are timing-only builds
+// without the output stores, the selection, the B operand's LDS reads or the A operand's loads
+// (its CT_NOTAB went with the table build, item 7).
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ void conv_load_a(const double* __restrict__ X, int ldr, int kb, int g, double (&v)[4]) {
 #ifdef BO_ABL_CT_ACONST
@@ -531,11 +590,14 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
 #else
   const bool outs = a.ld_out < 0;                                // ablation (timing only): false, and not known to be
 #endif
-  for (int t = tid; t < a.NP; t += nt) cn[t] = t < a.n ? a.rc[2 * a.order[t] + 1] : 0;
+  for (int t = tid; t < a.NP; t += nt) {
+    const int n = t < a.n ? a.order[t] : -1;
+    cn[t] = n >= 0 ? a.rc[2 * n + 1] | (a.rc[2 * n] << 16) : 0;
+  }
 
   double lv = -__builtin_inf();                                  // the wave's top-q list, lanes 0..q-1
   long long li = -1;
-  double tab_nhl = __builtin_nan("");                            // length scale of the tables in LDS
+  int tab_ix = -1;                                               // the objective whose tables are in LDS
   for (long long base = (long long)blockIdx.x * W; base < n_wt; base += (long long)gridDim.x * W) {
     const long long wt = base + wave;
     const bool active = wt < n_wt;
@@ -543,53 +605,20 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
     const int i0 = (int)(wtc / cb_n) * 16, j0 = (int)(wtc % cb_n) * TW;
     double acq[NB][4];
     for (int o = 0; o < a.n_obj; ++o) {
-      // the tables depend on the length scale alone: rebuilt only when it changes (one objective,
-      // or equal length scales: built once per workgroup; objectives with different length scales
-      // on a grid of more wave tiles than 4 gridDim.x rebuild them per tile and objective, since
+      // the tables depend on the length scale alone: copied only when it changes (one objective,
+      // or equal length scales: once per workgroup; objectives with different length scales
+      // on a grid of more wave tiles than 4 gridDim.x copy them per tile and objective, since
       // the acquisition sums the objectives of a tile in registers)
-      const double nhl = a.nhl[o];
-      if (!(nhl == tab_nhl)) {
+      const int tx = a.tix[o];
+      if (tx != tab_ix) {
         __syncthreads();                                         // the previous tables are done with
-        // entries below kTabFlush become +0.0 (a NaN entry compares false and stays); the band is
-        // the largest |t| that the same comparison kept
-        int mq = 0;
-        int mm = 0;
-#ifndef BO_ABL_CT_NOTAB
-        for (int t = tid; t < 2 * L.HB; t += nt) {
-          const int par = t >= L.HB ? 1 : 0, h = t - par * L.HB;
-          const int mi = 2 * h + par - (a.LT - 1);
-          const double m = (double)mi;
-          const double v = exp(0.5 * nhl * (m * m));
-          const bool flush = v < kTabFlush;
-          tabB[t] = flush ? 0.0 : v;
-          if (!flush) mq = max(mq, abs(mi));
-        }
-        for (int t = tid; t < a.Cpad + a.C - 1; t += nt) {
-          const int mi = t - (a.C - 1);
-          const double m = (double)mi;
-          const double v = exp(nhl * (m * m));
-          const bool flush = v < kTabFlush;
-          tabH[t] = flush ? 0.0 : v;
-          if (!flush) mm = max(mm, abs(mi));
-        }
-#else
-        // ablation (timing only): the tables stay as they are; the bands from the flush threshold in closed form
-        mm = min((int)sqrt(128.0 * 0.6931471805599453 / -nhl), a.C - 1);
-        mq = min((int)sqrt(256.0 * 0.6931471805599453 / -nhl), a.LT - 1);
-#endif
-        if (tid < 2) hband[tid] = 0;
-        __syncthreads();
-#pragma unroll
-        for (int d = 32; d > 0; d >>= 1) {
-          mq = max(mq, __shfl_xor(mq, d, 64));
-          mm = max(mm, __shfl_xor(mm, d, 64));
-        }
-        if (lane == 0) {
-          atomicMax(hband, mq);                                  // (integer maxima: no order in them)
-          atomicMax(hband + 1, mm);
-        }
-        __syncthreads();                                         // hband stays until the next build
-        tab_nhl = nhl;
+        // the list kernel's image of tabB | tabH | hband, 16 bytes per load (and a last double of its own
+        // when their doubles are odd: cn[] starts behind it)
+        const double* src = a.ctab + (size_t)tx * conv_ctab_doubles(a.C, a.Cpad, a.LT);
+        for (int t = tid; t < L.cn / 2; t += nt) ((double2*)sd)[t] = ((const double2*)src)[t];
+        if ((L.cn & 1) && tid == 0) sd[L.cn - 1] = src[L.cn - 1];
+        __syncthreads();                                         // hband stays until the next copy
+        tab_ix = tx;
       }
       // variance k-blocks: those that hold a tau with E(2j - tau) != 0 for a column of the tile,
       // tau in [2 j0 - hq, 2 (j0 + TW - 1) + hq]; the others multiply T by exact zeros.  (A tile of padding
@@ -658,7 +687,7 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
         const double* ph = tabH + j0 + jl + (a.C - 1);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
-          const double* p = ph - c4[s];
+          const double* p = ph - (c4[s] & 0xffff);
 #pragma unroll
           for (int nb = 0; nb < NB; ++nb) bv[s][nb] = p[16 * nb];
         }
@@ -719,9 +748,10 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
     if (select) {
       // the wave's list and the tile's 256 NB candidates, merged by rounds of extract-best: each lane
       // offers the best of its remaining candidates (and its list entry), the wave takes the best
-      // offer (NaN first, then descending, ties by ascending index); a winner that is an evaluated
-      // point (the prep launch's hash set, compared exactly) is dropped and the round repeated.
-      // Skipped when no candidate comes before the list's last entry.
+      // offer (NaN first, then descending, ties by ascending index).  Evaluated points never win: when they
+      // are the call's training points (excl_train) the tile's are taken out before the rounds; with an
+      // exclusion set of the caller's a winner found in the prep launch's hash set (compared exactly) is
+      // dropped and the round repeated.  Skipped when no candidate comes before the list's last entry.
       const int q = a.topq;
       const unsigned long long kq = bo_readlane_u(bo_order_key(lv, li), q - 1);
       const long long iq = bo_readlane_i(li, q - 1);
@@ -733,6 +763,24 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
           beats = beats || bo_key_before(bo_order_key(acq[nb][r], gis[nb][r]), gis[nb][r], kq, iq);
       if (__ballot(beats) != 0ull) {
         unsigned int taken = 0;                                  // bit 16: the list entry
+        if (a.excl_train) {
+          // the evaluated points are the training points: those of the tile's columns are the slice
+          // cstart[j0] .. cstart[j0 + TW] - 1 of cn[], 64 a step and a lane each; the few in the tile's rows
+          // are passed round one by one, and the lane that owns the candidate (D row g + 4 r, column jl of
+          // block nb) takes it out of the rounds
+          const int s_hi = __builtin_amdgcn_readfirstlane(a.cstart[j0 + TW < a.C ? j0 + TW : a.C]);
+          for (int s0 = __builtin_amdgcn_readfirstlane(a.cstart[j0 < a.C ? j0 : a.C]); s0 < s_hi; s0 += 64) {
+            const int e = s0 + lane < s_hi ? cn[s0 + lane] : 0;
+            const int dr = (e >> 16) - (a.row_lo + i0), dc = (e & 0xffff) - j0;
+            unsigned long long hits = __ballot(s0 + lane < s_hi && dr >= 0 && dr < 16);
+            while (hits != 0ull) {
+              const int src = __builtin_ctzll(hits);
+              hits &= hits - 1ull;
+              const int hr = __builtin_amdgcn_readlane(dr, src), hc = __builtin_amdgcn_readlane(dc, src);
+              if (lane == 16 * (hr & 3) + (hc & 15)) taken |= 1u << (4 * (hc >> 4) + (hr >> 2));
+            }
+          }
+        }
         double nv = -__builtin_inf();
         long long ni = -1;
         int filled = 0;
@@ -766,7 +814,7 @@ __global__ __launch_bounds__(64 * kContractWaves) void conv_contract_kernel(cons
           bool excluded = false;
           if (win) {
             taken |= 1u << bs;
-            if (bs != 16) {
+            if (bs != 16 && !a.excl_train) {
               const long long row = wi / a.C, c = wi - row * a.C;
               double co[BO_MAX_DIM] = {(double)(a.lo0 + row), (double)(a.lo1 + c), 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
               excluded = bo_hash_contains(a.hkeys, a.hidx, a.hmask, a.excl_pts, 2, co, 2);
@@ -844,6 +892,7 @@ namespace bo {
 bool conv_lds_admits(int n, int R, int C, int Cpad, int LT, int NP) {
   const size_t bound = ((size_t)4 * R + 2048) * sizeof(double) + ((size_t)(C + 1) + 3 * (size_t)n + 2048) * sizeof(int);
   assert(ConvSetupLds(n, C, 256).bytes <= bound && ListLds(n, C).bytes <= bound && AccLds(R).bytes <= bound);
+  assert(ContractLds(C, Cpad, LT, NP).hband == conv_ctab_band(C, Cpad, LT));   // the workspace's image of the tables
   return bound <= kConvLdsBytes && ContractLds(C, Cpad, LT, NP).bytes <= kConvLdsBytes;
 }
 
@@ -886,8 +935,11 @@ hipError_t launch_gridconv(const ConvArgs& ca, const ConvPlan& cp, const ConvSch
   const int tau_blocks = (ca.LT + kListWaves - 1) / kListWaves;    // the padding tau too: their pkept
   const long long tm_elems = (long long)ca.NP * ca.ldr;
   const int tm_blocks = (int)((tm_elems + 1023) / 1024 < 512 ? (tm_elems + 1023) / 1024 : 512);
-  hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks), dim3(64 * kListWaves), l1, st, ca, tau_blocks,
-                     sc.dyn);
+  // a thread per entry of the longer of the E tables, up to 64 blocks
+  const long long tab_elems = 4LL * ca.R > 2LL * ca.Cpad + ca.LT ? 4LL * ca.R : 2LL * ca.Cpad + ca.LT;
+  const int tab_blocks = (int)((tab_elems + 255) / 256 < 64 ? (tab_elems + 255) / 256 : 64);
+  hipLaunchKernelGGL(conv_list_kernel, dim3(tau_blocks + tm_blocks + tab_blocks), dim3(64 * kListWaves), l1, st, ca,
+                     tau_blocks, tm_blocks, sc.dyn);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(conv_acc_kernel, dim3((unsigned)sc.wgs, ca.n_obj), dim3(64 * kConvAccWaves), la, st, ca,
                      (const double*)ca.pair_w, (const int*)ca.pair_sl, (const int*)ca.pstart, (const int*)ca.pkept,

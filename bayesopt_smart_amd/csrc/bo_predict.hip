@@ -566,7 +566,7 @@ void plan_gridconv(const bo_predict_desc* d, Plan* pl, bool kmem, int cus) {
 #endif
   if (wgs > (long long)pl->grid * pl->waves) wgs = (long long)pl->grid * pl->waves;
   cp.grid = (int)wgs;
-  cp.ws = bo::conv_layout(n, d->n_obj, C, cp.LT, cp.NP, cp.ldr, align256(pl->total));
+  cp.ws = bo::conv_layout(n, d->n_obj, R, C, cp.Cpad, cp.LT, cp.NP, cp.ldr, align256(pl->total));
   pl->total = cp.ws.end;
   pl->conv = cp;
 }
@@ -881,6 +881,14 @@ static void fill_conv_args(const bo_predict_desc* d, const Plan& pl, char* ws, c
   ca.T = (double*)(ws + L.T);
   ca.pair_sl = (int*)(ws + L.pair_sl);
   ca.pair_w = (double*)(ws + L.pair_w);
+  ca.tabE = (double*)(ws + L.tabE);
+  ca.ctab = (double*)(ws + L.ctab);
+  // an objective reads the tables of the first objective whose length scale has the same bits as its own
+  for (int o = 0; o < d->n_obj; ++o) {
+    int t = 0;
+    while (memcmp(&ca.nhl[t], &ca.nhl[o], sizeof(double)) != 0) ++t;
+    ca.tix[o] = t;
+  }
   ca.n_pairs = (int)(d->n_train * (d->n_train + 1) / 2);
   ca.full = (d->mode & BO_PREDICT_GRID_CONV_FULL) ? 1 : 0;
   ca.mu = fa.mu;
@@ -892,6 +900,7 @@ static void fill_conv_args(const bo_predict_desc* d, const Plan& pl, char* ws, c
   ca.topq = d->topq;
   ca.partial = fa.partial;
   ca.n_lists = pl.grid * pl.waves;
+  ca.excl_train = fa.excl ? 0 : 1;
   ca.excl_pts = fa.excl ? fa.excl : fa.xpad;
   ca.hkeys = fa.hkeys;
   ca.hidx = fa.hidx;

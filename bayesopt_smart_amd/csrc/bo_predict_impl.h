@@ -104,6 +104,11 @@ struct ConvArgs {
                                          // their list waves finished (an order of work, in no value)
   int* ticket;                           // [BO_MAX_OBJ][kConvTicketGroups] (stride kConvTicketStride): the next
                                          // work item of each group of the accumulate kernel's workgroups
+  int tix[BO_MAX_OBJ];                   // the objective whose tables objective o reads: the first with a length
+                                         // scale bit-equal to its own (the host decides it from the call's arguments)
+  double* tabE;                          // [n_obj][4R] the accumulate kernel's E table per objective (its own tix only)
+  double* ctab;                          // [n_obj][conv_ctab_doubles] the contraction's tables per objective (its own
+                                         // tix only), as ContractLds lays them out: tabB | tabH | the band words hq, hm
   int n_pairs;                           // n (n + 1) / 2: pairs n <= m, every one in exactly one tau
   int* pair_sl;                          // [n_pairs] table base of r_n + r_m, tau-major list order
   double* pair_w;                        // [n_obj][n_pairs] w_nm
@@ -114,6 +119,8 @@ struct ConvArgs {
   int full;                              // BO_PREDICT_GRID_CONV_FULL: every k-block of both GEMMs
   TopEntry* partial;                     // [n_lists][topq]
   int n_lists;                           // lists the merge reads (those past the grid's are emptied)
+  int excl_train;                        // the call excludes its own training points: the contraction marks them from
+                                         // its LDS copy of their coordinates and probes no hash set
   const double* excl_pts;                // rows the hash set indexes ([*][2])
   const unsigned long long* hkeys;
   const int* hidx;
@@ -135,6 +142,16 @@ constexpr int kConvClasses = 64;
 constexpr int kConvShards = BO_CONV_SHARDS;   // counters per class (tau % kConvShards): a power of two <= 16
 constexpr int kConvCountStride = 32;     // ints between two classes' counters (one 128-byte line each)
 constexpr int kConvAccWaves = 4;         // waves per workgroup of the accumulate kernel
+
+// Doubles of one objective's contraction tables in the workspace: ContractLds' tabB[2][Cpad + LT / 2] |
+// tabH[Cpad + C - 1] | the two band words in one double (bo_gridconv.hip), to a whole 16 bytes.
+// conv_ctab_band is the double that holds the band words.
+__host__ __device__ inline long long conv_ctab_band(long long C, long long Cpad, long long LT) {
+  return 2 * (Cpad + LT / 2) + Cpad + C - 1;
+}
+__host__ __device__ inline long long conv_ctab_doubles(long long C, long long Cpad, long long LT) {
+  return (conv_ctab_band(C, Cpad, LT) + 1 + 1) / 2 * 2;
+}
 
 // The accumulate kernel's persistent grid (conv_acc_schedule): decided on the host before the prep
 // launch, whose setup block starts the tickets for it.
@@ -184,7 +201,8 @@ __device__ __forceinline__ void conv_scan(int* v, int len, int* part, int* out) 
 // Setup of the grid-convolution path, one workgroup of THREADS (a role block of the prep launch):
 // rc[n] = integer (row, column) of training point n; cstart / order = the points bucketed by column,
 // ascending n inside a bucket (the pair list's order, and with it T's bits, follow it); the start
-// values of the accumulate kernel's tickets and the zeroed class counters.
+// values of the accumulate kernel's tickets, the zeroed class counters and the zeroed band words of the
+// contraction's tables (the list kernel's table blocks raise them).
 // The block runs beside the one that checks that every training point is a grid point, so it cannot
 // know the answer: a coordinate is clamped into the grid (a NaN to 0), which changes nothing for a
 // grid point and keeps every index in range otherwise -- then the flag stops the kernels that would
@@ -209,6 +227,10 @@ __device__ __forceinline__ void conv_setup_block(const ConvArgs& a, const ConvSc
   }
   for (int t = tid; t < kConvClasses * kConvShards; t += THREADS)
     a.ccount[t / kConvShards * kConvCountStride + t % kConvShards] = 0;
+  if (tid < a.n_obj) {
+    // (both words: the bits of +0.0)
+    a.ctab[tid * conv_ctab_doubles(a.C, a.Cpad, a.LT) + conv_ctab_band(a.C, a.Cpad, a.LT)] = 0.0;
+  }
   __syncthreads();
   for (int n = tid; n < a.n; n += THREADS) {
     // (fmax / fmin return the other operand for a NaN)
@@ -251,11 +273,11 @@ __device__ __forceinline__ void conv_setup_block(const ConvArgs& a, const ConvSc
 // Byte offsets of the grid-convolution path's workspace arrays (ConvArgs describes them), from `base`.  The one
 // description of that part of the workspace: the plan's total and every pointer of predict_impl come from it.
 struct ConvLayout {
-  size_t cstart, order, rc, pstart, pkept, clist, ticket, ccount, Tm, T, pair_sl, pair_w, end;
+  size_t cstart, order, rc, pstart, pkept, clist, ticket, ccount, Tm, T, pair_sl, pair_w, tabE, ctab, end;
 };
 
-inline ConvLayout conv_layout(long long n, int n_obj, long long C, long long LT, long long NP, long long ldr,
-                              size_t base) {
+inline ConvLayout conv_layout(long long n, int n_obj, long long R, long long C, long long Cpad, long long LT,
+                              long long NP, long long ldr, size_t base) {
   size_t at = base;
   auto take = [&at](long long count, size_t elem, size_t align) {
     const size_t off = (at + align - 1) / align * align;
@@ -276,9 +298,12 @@ inline ConvLayout conv_layout(long long n, int n_obj, long long C, long long LT,
   L.T = take(n_obj * LT * ldr, sizeof(double), 256);
   L.pair_sl = take(pairs, sizeof(int), 256);
   L.pair_w = take(n_obj * pairs, sizeof(double), 256);
-  // callers and captured graphs hold workspaces of the size that earlier versions returned; those kept 128 spare
-  // bytes in front of the tickets, a 256-byte line more whenever the tickets start on one: padded to that size
-  L.end = take(0, 1, 256) + (L.ticket % 256 == 0 ? 256 : 0);
+  // the arrays up to here end where earlier versions' workspace ended (those kept 128 spare bytes in front of the
+  // tickets, a 256-byte line more whenever the tickets start on one); the tables come behind that
+  at = take(0, 1, 256) + (L.ticket % 256 == 0 ? 256 : 0);
+  L.tabE = take(n_obj * 4 * R, sizeof(double), 256);
+  L.ctab = take(n_obj * conv_ctab_doubles(C, Cpad, LT), sizeof(double), 256);
+  L.end = take(0, 1, 256);
   return L;
 }
 
