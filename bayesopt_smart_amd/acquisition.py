@@ -150,10 +150,45 @@ def _record_indices(rec, q):
     return idx[idx >= 0]
 
 
-def _front_of(y_vector, n_evaluations, reference_point):
-    """The Pareto-efficient rows (device filter, pareto.py:12-45) of y_vector[:n_evaluations], host."""
+def check_constraint_bounds(constraint_bounds, n_constraints=None):
+    """The outcome constraints' bounds as a float64 array [n_con, 2] (lo, hi), checked by the rules of
+    bo_constrained_ehvi: lo <= hi, neither NaN, each infinite on its own side only."""
+    b = np.asarray([] if constraint_bounds is None else constraint_bounds, dtype=np.float64).reshape(-1, 2)
+    if n_constraints is not None and b.shape[0] != n_constraints:
+        raise ValueError(f"constraint_bounds must hold one (lo, hi) pair per constraint: got {b.shape[0]} "
+                         f"for n_constraints={n_constraints}")
+    for j, (lo, hi) in enumerate(b):
+        if np.isnan(lo) or np.isnan(hi):
+            raise ValueError(f"constraint {j}: a bound is NaN (use -inf / +inf for a one-sided constraint)")
+        if lo > hi:
+            raise ValueError(f"constraint {j}: the lower bound {lo} exceeds the upper bound {hi}: no value is feasible")
+        if lo == np.inf or hi == -np.inf:
+            raise ValueError(f"constraint {j}: lo = +inf or hi = -inf leaves no feasible value")
+    return b
+
+
+def feasible_rows(y, n_obj, constraint_bounds):
+    """Host bool array [len(y)]: the rows of y ([n, n_obj + n_con], objectives first) whose constraint
+    outputs all lie inside their bounds, lo_j <= y[:, n_obj + j] <= hi_j (a NaN output is infeasible).
+    The one statement of feasibility: the loop's front and pareto_analysis both use it."""
+    y = np.asarray(y.cpu().numpy() if isinstance(y, torch.Tensor) else y, dtype=np.float64)
+    b = check_constraint_bounds(constraint_bounds)
+    y = y.reshape(-1, n_obj + b.shape[0])
+    g = y[:, n_obj:]
+    return np.all((g >= b[:, 0]) & (g <= b[:, 1]), axis=1)
+
+
+def _front_of(y_vector, n_evaluations, reference_point, constraint_bounds=None):
+    """The Pareto-efficient rows (device filter, pareto.py:12-45) of y_vector[:n_evaluations], host.
+    With constraint_bounds: of the feasible rows only (feasible_rows), over the objective columns
+    (the first len(reference_point)) only."""
     from .pareto import is_pareto_efficient
     y = y_vector[:n_evaluations]
+    if constraint_bounds is not None:
+        n_obj = len(reference_point)
+        y = np.asarray(y.cpu().numpy() if isinstance(y, torch.Tensor) else y)
+        y = np.ascontiguousarray(y[feasible_rows(y, n_obj, constraint_bounds)][:, :n_obj])
+        n_evaluations = y.shape[0]
     front = y[is_pareto_efficient(y)] if n_evaluations > 0 else np.zeros((0, len(reference_point)))
     return front.cpu().numpy() if isinstance(front, torch.Tensor) else front
 
@@ -391,11 +426,64 @@ def expected_hypervolume_improvement(mu, var, front, reference_point, out=None, 
     return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
 
 
+def constrained_expected_hypervolume_improvement(mu, var, front, reference_point, constraint_bounds, out=None,
+                                                 pof_out=None, form="auto", tables=None):
+    """The feasibility-weighted EHVI of every candidate (bo_constrained_ehvi; include/bo_amd.h states
+    the quantity, its limits and its rounding rule).  mu / var: [n_obj + n_con, M], the objective
+    rows first (n_obj = len(reference_point), or tables.n_obj), numpy or HIP tensors.
+    constraint_bounds: n_con pairs (lo, hi), either infinite on its own side.  `front`: the FEASIBLE
+    evaluated points' objective vectors.  acq = EHVI(objective rows over `front`) * prod_j P_j,
+    P_j = P(lo_j <= Y_j <= hi_j); `pof_out` ([M]) receives prod_j P_j.  `form` / `tables` as
+    expected_hypervolume_improvement's (same bits).  No constraints: the plain EHVI's bits.
+    Returns acq ([M], a device tensor, or numpy for numpy `mu`); written into `out` when given."""
+    if form not in EHVI_FORMS:
+        raise ValueError(f"unknown form {form!r} (expected 'auto', 'direct' or 'table')")
+    bounds = check_constraint_bounds(constraint_bounds)
+    n_con = bounds.shape[0]
+    dev = _dev_of(out, mu)
+    m = _Arg(mu, dev)
+    v = _Arg(var, dev)
+    if m.t.dim() != 2 or v.t.shape != m.t.shape or m.t.stride(1) != 1 or v.t.stride() != m.t.stride():
+        raise ValueError("mu / var must both be [n_obj + n_con, M] with one row stride")
+    n_out, n = m.t.shape
+    tb = tables if tables is not None else EhviTables(front, reference_point, dev)
+    n_obj = tb.n_obj
+    if n_obj + n_con != n_out:
+        raise ValueError(f"the front has {n_obj} objectives and there are {n_con} constraints, mu has {n_out} rows")
+    acq = _Arg(out, dev, write=True) if out is not None else None
+    dst = acq.t if acq is not None else torch.empty(n, dtype=F64, device=dev)
+    if dst.numel() != n:
+        raise ValueError(f"out holds {dst.numel()} values for {n} candidates")
+    pof = _Arg(pof_out, dev, write=True) if pof_out is not None else None
+    if pof is not None and pof.t.numel() != n:
+        raise ValueError(f"pof_out holds {pof.t.numel()} values for {n} candidates")
+    nb = tb.n_boxes
+    _lib.check(_lib.load().bo_constrained_ehvi(
+        dst.data_ptr(), pof.ptr if pof is not None else None, m.ptr, v.ptr, m.t.stride(0), n, n_obj, n_con,
+        _host_vec(bounds[:, 0], n_con), _host_vec(bounds[:, 1], n_con),
+        tb.boxes.data_ptr() if nb else None, nb, tb.edges.data_ptr() if nb else None, tb.n_edges,
+        tb.box_idx.data_ptr() if nb else None, EHVI_FORMS[form], stream_handle(dev)), "bo_constrained_ehvi")
+    if pof is not None:
+        pof.finish()
+    if acq is not None:
+        acq.finish()
+        return out
+    return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
+
+
 def update_expected_hypervolume_improvement(acquisition_values, mu_objectives, variance_objectives, y_vector,
-                                            n_evaluations, reference_point):
+                                            n_evaluations, reference_point, constraint_bounds=None):
     """The acquisition update of the loop (bayesian_optimization.py:195-199) as the EHVI: the front
     is the Pareto-efficient subset (device filter, pareto.py:12-45) of the evaluated objectives
-    y_vector[:n_evaluations]; in place into `acquisition_values`."""
+    y_vector[:n_evaluations]; in place into `acquisition_values`.  With `constraint_bounds` (y_vector
+    and mu / variance then carry the constraint outputs after the objectives): the constrained EHVI
+    over the front of the feasible evaluated points."""
+    if constraint_bounds is not None:
+        constrained_expected_hypervolume_improvement(
+            mu_objectives, variance_objectives,
+            _front_of(y_vector, n_evaluations, reference_point, constraint_bounds), reference_point,
+            constraint_bounds, out=acquisition_values)
+        return
     expected_hypervolume_improvement(mu_objectives, variance_objectives,
                                      _front_of(y_vector, n_evaluations, reference_point), reference_point,
                                      out=acquisition_values)
@@ -403,7 +491,7 @@ def update_expected_hypervolume_improvement(acquisition_values, mu_objectives, v
 
 def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, y_vector, n_evaluations,
                         reference_point, cands, evaluated_points, batch_size, offset=0, return_record=False,
-                        mask=None):
+                        mask=None, constraint_bounds=None):
     """The EHVI acquisition and its batch selection over one shard, in two launches: the EHVI scan
     into acquisition_values (device, [count]: the candidates [offset, offset + count) of `cands`,
     over the Pareto front of y_vector[:n_evaluations]), then bo_select_topq_masked over the shard's
@@ -411,16 +499,24 @@ def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, 
     call).  batch_size <= BO_MAX_TOPQ.  Returns the global indices of the shard's best batch_size
     candidates not equal to an evaluated point (select_next_batch's order, NaN first) -- or,
     `return_record`, the device record block [2 batch_size] (values, bit-cast int64 indices) for
-    the multi-rank exchange, as hvi_select_indices."""
+    the multi-rank exchange, as hvi_select_indices.  With `constraint_bounds` the scan is the
+    constrained EHVI (constrained_expected_hypervolume_improvement) over the front of the feasible
+    rows of y_vector; infeasible evaluated points stay excluded like any evaluated point."""
     if batch_size > _lib.MAX_TOPQ:
         raise ValueError(f"ehvi_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
     dev = _dev_of(acquisition_values, mu_objectives)
     acq = _Arg(acquisition_values, dev, write=True)
     n = acq.t.numel()
     mask = _shard_mask(mask, cands, offset, n, dev, evaluated_points, "ehvi_select_indices")
-    expected_hypervolume_improvement(mu_objectives, variance_objectives,
-                                     _front_of(y_vector, n_evaluations, reference_point), reference_point,
-                                     out=acq.t)
+    if constraint_bounds is not None:
+        constrained_expected_hypervolume_improvement(
+            mu_objectives, variance_objectives,
+            _front_of(y_vector, n_evaluations, reference_point, constraint_bounds), reference_point,
+            constraint_bounds, out=acq.t)
+    else:
+        expected_hypervolume_improvement(mu_objectives, variance_objectives,
+                                         _front_of(y_vector, n_evaluations, reference_point), reference_point,
+                                         out=acq.t)
     rec = torch.empty(2 * batch_size, dtype=F64, device=dev)
     lib = _lib.load()
     ws = Workspace.get(lib.bo_select_topq_workspace_size(n, batch_size), dev)

@@ -29,8 +29,9 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, _record_indices, ehvi_select_indices,
-                          hvi_select_indices, select_batch_bucb, select_batch_kb, select_batch_ts,
+from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, _record_indices, check_constraint_bounds,
+                          ehvi_select_indices, feasible_rows, hvi_select_indices, select_batch_bucb,
+                          select_batch_kb, select_batch_ts,
                           select_indices, thompson_draws,
                           update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
 
@@ -218,7 +219,8 @@ class DeviceBackend:
                 "std_var": b.std_variance_objectives, "ucb": b.ucb, "acq": b.acquisition_values}
 
     def select(self, fitted, prior_mean, prior_variance, length_scales, betas, batch_size, evaluated,
-               acquisition="sum_ucb", y_evaluated=None, reference_point=None, batch_strategy="top"):
+               acquisition="sum_ucb", y_evaluated=None, reference_point=None, batch_strategy="top",
+               constraint_bounds=None):
         """Global candidate indices of the next batch (select_next_batch's order, the evaluated
         points excluded).  "sum_ucb" is the reference's acquisition (acquisition.py:89-108, fused
         top-q); "hvi" replaces the acquisition array with the exact hypervolume improvement of the
@@ -235,8 +237,16 @@ class DeviceBackend:
         collective is needed for them and the exchange of the top-q records merges the shards;
         "kb" (not in the reference; "ehvi" only, one rank) takes every pick after the first from
         the EHVI of the variance conditioned on the earlier picks over the front extended by the
-        posterior means at those picks (Kriging believer, acquisition.select_batch_kb)."""
+        posterior means at those picks (Kriging believer, acquisition.select_batch_kb).
+        `constraint_bounds` (not in the reference; "ehvi" and "top" only): the last
+        len(constraint_bounds) outputs are outcome constraints, y_evaluated carries them after the
+        objectives, and the acquisition is the EHVI over the front of the feasible evaluated
+        points times the probability of feasibility
+        (acquisition.constrained_expected_hypervolume_improvement)."""
         _check_acquisition(acquisition)
+        if constraint_bounds is not None:
+            _check_constraints(len(prior_mean) - len(constraint_bounds), len(constraint_bounds), constraint_bounds,
+                               acquisition, batch_strategy)
         _check_batch_strategy(batch_strategy, acquisition, batch_size, self.group)
         xd, yd, kinv = fitted
         out = self._outputs()
@@ -301,7 +311,8 @@ class DeviceBackend:
                 rec = ehvi_select_indices(self.bufs.acquisition_values, self.bufs.mu_objectives,
                                           self.bufs.variance_objectives, y_evaluated, len(y_evaluated),
                                           reference_point, self.cands, evaluated, batch_size,
-                                          offset=self.offset, return_record=True, mask=self._excl_mask)
+                                          offset=self.offset, return_record=True, mask=self._excl_mask,
+                                          constraint_bounds=constraint_bounds)
             from .distributed import collectives_on, exchange_topq_rec
             if not collectives_on(self.group):
                 return _record_indices(rec, batch_size)
@@ -313,7 +324,8 @@ class DeviceBackend:
         if acquisition == "ehvi":
             update_expected_hypervolume_improvement(self.bufs.acquisition_values, self.bufs.mu_objectives,
                                                     self.bufs.variance_objectives, y_evaluated,
-                                                    len(y_evaluated), reference_point)
+                                                    len(y_evaluated), reference_point,
+                                                    constraint_bounds=constraint_bounds)
         # batches above BO_MAX_TOPQ: rounds of the standalone device selection (over the gathered
         # array when sharded)
         from .distributed import collectives_on
@@ -338,7 +350,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
              callbacks: Optional[List[Callable]] = None, *,
              acquisition: str = "sum_ucb", group=None, backend=None,
              float_type=None, batch_strategy: str = "top", ts_features: int = 1024,
-             ts_seed: int = 0) -> Tuple[np.ndarray, np.ndarray, int]:
+             ts_seed: int = 0, constraint_bounds=None) -> Tuple[np.ndarray, np.ndarray, int]:
     """bayesian_optimization.py:51-247 with the reference's argument list.
 
     `kernel_matrices` and the posterior arrays may be HIP tensors (in place) or numpy arrays;
@@ -361,6 +373,12 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     backend's when `backend` is given); "kb" by a Kriging believer for the EHVI (acquisition "ehvi"
     only, one rank, batch_size <= BO_MAX_TOPQ): each pick joins the front as a believed observation
     equal to the posterior mean; "top", the default, is the reference's batch.
+    `constraint_bounds` (n_con pairs (lo, hi); acquisition "ehvi" and batch_strategy "top" only):
+    the last n_con of the len(prior_mean) outputs are outcome constraints -- `function` returns
+    them after the objectives, y_vector and the posterior arrays carry them as further columns /
+    rows, reference_point has one coordinate per objective -- and the acquisition is the EHVI over
+    the front of the feasible evaluated points times the probability of feasibility
+    (DeviceBackend.select).
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -369,6 +387,9 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     del k_star, n_objectives, bounds  # unused, as in the reference (reference_point too, unless
     #                                   acquisition="hvi" / "ehvi", the exact / expected hypervolume improvement)
     n_obj = len(prior_mean)
+    if constraint_bounds is not None:
+        _check_constraints(n_obj - len(constraint_bounds), len(constraint_bounds), constraint_bounds, acquisition,
+                           batch_strategy)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, getattr(backend, "group", group))
     if backend is None:
         dev = require_device()
@@ -417,6 +438,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         t2 = time.perf_counter()
         # the default strategy is not passed on: a caller's backend keeps the interface it has
         strat = {} if batch_strategy == "top" else {"batch_strategy": batch_strategy}
+        if constraint_bounds is not None:   # likewise, only when set
+            strat["constraint_bounds"] = constraint_bounds
         idx = backend.select(fitted, prior_mean, prior_variance, length_scales, betas, batch_size,
                              x_vector[:current_eval], acquisition, y_vector[:current_eval], reference_point,
                              **strat)
@@ -501,9 +524,41 @@ def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
                          "all-gather of the per-rank best candidates")
 
 
-def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", batch_strategy="top", group=None):
+def _check_constraints(n_obj, n_con, constraint_bounds, acquisition, batch_strategy):
+    """What outcome constraints do not cover raises here, with the reason; then the bounds' own
+    rules (acquisition.check_constraint_bounds)."""
+    if n_con < 0:
+        raise ValueError(f"n_constraints must be >= 0 (got {n_con})")
+    if n_con == 0 and constraint_bounds is None:
+        return
+    if acquisition != "ehvi":
+        why = {"sum_ucb": "'sum_ucb' takes negative values, so its product with a probability of feasibility "
+                          "does not order the candidates",
+               "hvi": "'hvi' scores UCB vectors, not a posterior that a probability of feasibility could weight"}
+        raise ValueError("outcome constraints need acquisition='ehvi': "
+                         f"{why.get(acquisition, repr(acquisition) + ' has no constrained form')}")
+    if batch_strategy != "top":
+        why = {"kb": "'kb' would have to condition the constraint GPs on the believed point and decide its "
+                     "feasibility",
+               "ts": "'ts' would have to sample the constraint GPs",
+               "bucb": "'bucb' is not defined for the EHVI"}
+        raise ValueError("outcome constraints need batch_strategy='top': "
+                         f"{why.get(batch_strategy, repr(batch_strategy) + ' has no constrained form')}")
+    if not 1 <= n_obj <= 4:
+        raise ValueError(f"outcome constraints need 1 <= n_objectives <= 4 (got {n_obj}): the expected "
+                         "hypervolume improvement's box decomposition is limited to n_obj <= 4")
+    if n_obj + n_con > _lib.MAX_OBJ:
+        raise ValueError(f"n_objectives + n_constraints must be <= {_lib.MAX_OBJ} (got {n_obj} + {n_con}): "
+                         "every output has its own GP in one predict call")
+    check_constraint_bounds(constraint_bounds, n_con)
+
+
+def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", batch_strategy="top", group=None,
+                  n_constraints=0, constraint_bounds=None):
     """Fail in the constructor -- before any objective evaluation -- on shapes the device path
-    cannot run (the reference would hit them only mid-loop, if at all)."""
+    cannot run (the reference would hit them only mid-loop, if at all).  n_obj counts the
+    objectives; the n_constraints outcome constraints are further outputs."""
+    _check_constraints(n_obj, n_constraints, constraint_bounds, acquisition, batch_strategy)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, group)
     if not 1 <= n_obj <= _lib.MAX_OBJ:
         raise ValueError(f"n_objectives must be in [1, {_lib.MAX_OBJ}] (got {n_obj})")
@@ -518,11 +573,12 @@ def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", 
     if batch_size < 1:
         raise ValueError("batch_size must be >= 1")
     d = _lib.PredictDesc()
-    d.n_obj, d.dim, d.n_train, d.n_cand, d.cand_kind, d.topq = n_obj, dim, total_samples, 1, _lib.CAND_GRID, 0
+    n_out = n_obj + n_constraints
+    d.n_obj, d.dim, d.n_train, d.n_cand, d.cand_kind, d.topq = n_out, dim, total_samples, 1, _lib.CAND_GRID, 0
     for k in range(dim):
         d.grid_shape[k] = 1
     lib = _lib.load()
-    if lib.bo_predict_workspace_size(d) == 0 or lib.bo_invert_k_workspace_size(n_obj, total_samples) == 0:
+    if lib.bo_predict_workspace_size(d) == 0 or lib.bo_invert_k_workspace_size(n_out, total_samples) == 0:
         raise ValueError(f"total_samples = {total_samples} exceeds the device path's limits "
                          f"(predict: N <= 16384 and n_obj N^2 doubles < 2 GiB)")
 
@@ -550,7 +606,14 @@ class BayesianOptimization:
     ranks need no collective for the draws; or "kb", with acquisition "ehvi" only: a Kriging
     believer, every pick after the first maximises the EHVI of the variance conditioned on the
     earlier picks over the front extended by the posterior means there,
-    acquisition.select_batch_kb).
+    acquisition.select_batch_kb), and ``n_constraints`` with ``constraint_bounds`` (outcome
+    constraints, acquisition "ehvi" and batch_strategy "top" only: ``function`` returns
+    n_objectives + n_constraints values, the objectives first; constraint j is feasible inside
+    constraint_bounds[j] = (lo, hi), either infinite on its own side; y_vector has
+    n_objectives + n_constraints columns and prior_mean / prior_variance / length_scales / betas
+    that length, reference_point has length n_objectives; the acquisition is the EHVI over the
+    front of the feasible evaluated points times the probability of feasibility, and
+    pareto_analysis reports the feasible front over the objective columns).
     With several ranks, each holds its shard of the posterior arrays, the initial design is drawn
     and evaluated on rank 0 (every rank draws the same RNG numbers, so the RNG stays in step) and
     broadcast, and the loop runs as `optimize` describes.
@@ -568,11 +631,15 @@ class BayesianOptimization:
         self.n_iterations = n_iterations
         cb = kwargs.get("callbacks", None)
         self.callbacks = [] if cb is None else (cb if isinstance(cb, list) else [cb])
-        self.prior_mean = np.array(kwargs.get("prior_mean", [DEFAULT_PRIOR_MEAN] * n_objectives), dtype=ft)
-        self.prior_variance = np.array(kwargs.get("prior_variance", [DEFAULT_PRIOR_VARIANCE] * n_objectives),
-                                       dtype=ft)
-        self.length_scales = np.array(kwargs.get("length_scales", [DEFAULT_LENGTH_SCALE] * n_objectives), dtype=ft)
-        self.betas = np.array(kwargs.get("betas", [DEFAULT_BETA] * n_objectives), dtype=ft)
+        self.n_constraints = int(kwargs.get("n_constraints", 0))
+        self.constraint_bounds = kwargs.get("constraint_bounds")
+        if self.n_constraints == 0 and self.constraint_bounds is not None and len(self.constraint_bounds) == 0:
+            self.constraint_bounds = None
+        n_out = n_objectives + max(self.n_constraints, 0)     # the GPs: objectives, then constraints
+        self.prior_mean = np.array(kwargs.get("prior_mean", [DEFAULT_PRIOR_MEAN] * n_out), dtype=ft)
+        self.prior_variance = np.array(kwargs.get("prior_variance", [DEFAULT_PRIOR_VARIANCE] * n_out), dtype=ft)
+        self.length_scales = np.array(kwargs.get("length_scales", [DEFAULT_LENGTH_SCALE] * n_out), dtype=ft)
+        self.betas = np.array(kwargs.get("betas", [DEFAULT_BETA] * n_out), dtype=ft)
         self.batch_size = kwargs.get("batch_size", DEFAULT_BATCH_SIZE)
         init_pts = kwargs.get("initial_points")
         if init_pts is not None:
@@ -599,10 +666,20 @@ class BayesianOptimization:
         if not 1 <= self.ts_features <= _lib.TS_MAX_FEATURES:
             raise ValueError(f"ts_features must be in [1, {_lib.TS_MAX_FEATURES}] (got {self.ts_features})")
         _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
-                      self.batch_strategy, self.group)
+                      self.batch_strategy, self.group, self.n_constraints, self.constraint_bounds)
+        self.reference_point = np.array(kwargs.get("reference_point", [0.0] * n_objectives), dtype=ft)
+        if self.constraint_bounds is not None:
+            self.constraint_bounds = check_constraint_bounds(self.constraint_bounds, self.n_constraints)
+            for name in ("prior_mean", "prior_variance", "length_scales", "betas"):
+                if len(getattr(self, name)) != n_out:
+                    raise ValueError(f"{name} must have one entry per output, n_objectives + n_constraints = "
+                                     f"{n_out} (got {len(getattr(self, name))})")
+            if len(self.reference_point) != n_objectives:
+                raise ValueError("reference_point must have one coordinate per objective, n_objectives = "
+                                 f"{n_objectives} (got {len(self.reference_point)}): constraints have none")
         self.x_vector = np.zeros((self.total_samples, self.dim), dtype=ft)
-        self.y_vector = np.zeros((self.total_samples, n_objectives), dtype=ft)
-        self._backend = DeviceBackend(self.candidates, n_objectives, self.total_samples, self.device,
+        self.y_vector = np.zeros((self.total_samples, n_out), dtype=ft)
+        self._backend = DeviceBackend(self.candidates, n_out, self.total_samples, self.device,
                                       group=self.group, float_type=ft, ts_features=self.ts_features,
                                       ts_seed=self.ts_seed)
         self._buffers = self._backend.bufs
@@ -610,7 +687,7 @@ class BayesianOptimization:
         rank, world = _world(self.group)
         # the objective runs on rank 0 only; the other ranks draw the same LHS numbers (their RNG
         # stays in step with rank 0's) and receive rank 0's design and values
-        fn = self.function if rank == 0 else (lambda _p: np.zeros(n_objectives))
+        fn = self.function if rank == 0 else (lambda _p: np.zeros(n_out))
         if init_pts is not None:
             for i in range(self.initial_samples):
                 self.x_vector[i] = init_pts[i]
@@ -623,11 +700,10 @@ class BayesianOptimization:
         _broadcast_np(self.x_vector[: self.n_evaluations], self.group, self.device)
         _broadcast_np(self.y_vector[: self.n_evaluations], self.group, self.device)
         if np.all(self.prior_mean == DEFAULT_PRIOR_MEAN):
-            self.prior_mean = K.compute_prior_mean(self.y_vector, self.n_evaluations, n_objectives).astype(ft)
+            self.prior_mean = K.compute_prior_mean(self.y_vector, self.n_evaluations, n_out).astype(ft)
         if np.all(self.prior_variance == DEFAULT_PRIOR_VARIANCE):
             self.prior_variance = K.compute_prior_variance(self.y_vector, self.n_evaluations,
-                                                           n_objectives).astype(ft)
-        self.reference_point = np.array(kwargs.get("reference_point", [0.0] * n_objectives), dtype=ft)
+                                                           n_out).astype(ft)
 
     # the reference's preallocated arrays, materialised on the host on demand
     @property
@@ -662,12 +738,16 @@ class BayesianOptimization:
             bounds=self.bounds, callbacks=self.callbacks if self.callbacks else None,
             acquisition=self.acquisition, group=self.group, backend=self._backend,
             float_type=self.float_type, batch_strategy=self.batch_strategy, ts_features=self.ts_features,
-            ts_seed=self.ts_seed)
+            ts_seed=self.ts_seed, constraint_bounds=self.constraint_bounds)
 
     def pareto_analysis(self) -> np.ndarray:
-        """bayesian_optimization.py:465-488."""
+        """bayesian_optimization.py:465-488.  With outcome constraints: the front of the feasible
+        evaluated points (acquisition.feasible_rows) over the objective columns."""
         ey = self.y_vector[: self.n_evaluations]
         ex = self.x_vector[: self.n_evaluations]
+        if self.constraint_bounds is not None:
+            ok = feasible_rows(ey, self.n_objectives, self.constraint_bounds)
+            ex, ey = ex[ok], np.ascontiguousarray(ey[ok][:, : self.n_objectives])
         px, py = compute_pareto_front(ex, ey)
         print_pareto_analysis(px, py)
         return py

@@ -44,6 +44,66 @@ __device__ __forceinline__ double ehvi_psi(double d, double sigma, double rs) {
   return __builtin_fma(sigma, h, fmax(d, 0.0));
 }
 
+// What the constrained scan reads besides EhviArgs (include/bo_amd.h, bo_constrained_ehvi): the
+// constraint outputs are the rows [n_obj, n_obj + n_con) of e.mu / e.var.
+struct EhviConArgs {
+  EhviArgs e;
+  double* pof;             // optional [n]: P, the product of the constraints' probabilities
+  int n_obj, n_con;
+  double lo[BO_MAX_OBJ - 1], hi[BO_MAX_OBJ - 1];
+};
+
+// The upper tail Q(z) = 1 - Phi(z) = erfc(z / sqrt 2) / 2: positive, and relatively accurate, for
+// every z (0 past z = 38.6, 1 at z = -inf).
+__device__ __forceinline__ double ehvi_tail(double z) { return 0.5 * erfc(z * 0.7071067811865476); }
+
+// P(lo <= Y <= hi), Y ~ N(mu, sigma^2), lo <= hi, either infinite on its own side, as a difference
+// of positive tail terms, so that the result keeps its relative accuracy in both tails:
+//   za = (lo - mu) / sigma, zb = (hi - mu) / sigma
+//   za > 0:  Q(za) - Q(zb)      zb < 0:  Q(-zb) - Q(-za)      else:  (1 - Q(zb)) - Q(-za)
+// sigma = 0 gives 1 inside [lo, hi] (the bounds included), else 0; (-inf, +inf) gives exactly 1;
+// NaN in mu or sigma gives NaN.
+__device__ __forceinline__ double ehvi_pof(double mu, double sigma, double lo, double hi) {
+  if (mu != mu || sigma != sigma) return __builtin_nan("");
+  if (sigma == 0.0) return (lo <= mu && mu <= hi) ? 1.0 : 0.0;
+  const double za = (lo - mu) / sigma, zb = (hi - mu) / sigma;
+  // the three cases share two tail evaluations: Q(t1) - Q(t2), or (1 - Q(t1)) - Q(t2)
+  const bool above = za > 0.0, below = !above && zb < 0.0;
+  const double q1 = ehvi_tail(above ? za : (below ? -zb : zb));
+  const double q2 = ehvi_tail(above ? zb : -za);
+  return ((above || below) ? q1 : 1.0 - q1) - q2;
+}
+
+// P = ((P_0 P_1) P_2) ... of candidate i, left to right; 1 without constraints.  The same
+// non-temporal loads as ehvi_load's; a lane past the end computes on mu = 0, var = 1.
+__device__ __forceinline__ double ehvi_pof_product(const EhviConArgs& c, long long i, bool valid) {
+  double p = 1.0;
+  for (int j = 0; j < c.n_con; ++j) {
+    const long long row = (long long)(c.n_obj + j) * c.e.ld + i;
+    const double mu = valid ? __builtin_nontemporal_load(c.e.mu + row) : 0.0;
+    const double v = valid ? __builtin_nontemporal_load(c.e.var + row) : 1.0;
+    const double pj = ehvi_pof(mu, sqrt(fabs(v)), c.lo[j], c.hi[j]);
+    p = j == 0 ? pj : p * pj;
+  }
+  return p;
+}
+
+// The argument of a scan kernel: EhviArgs for the plain instantiation, EhviConArgs for the
+// constrained one.  ehvi_finish turns the box sum h into the value stored: the plain scan's h, or
+// fl(h P) with P stored where asked for.
+template <bool CON> struct EhviScan { typedef EhviArgs Args; };
+template <> struct EhviScan<true> { typedef EhviConArgs Args; };
+
+__host__ __device__ __forceinline__ const EhviArgs& ehvi_base(const EhviArgs& a) { return a; }
+__host__ __device__ __forceinline__ const EhviArgs& ehvi_base(const EhviConArgs& a) { return a.e; }
+
+__device__ __forceinline__ double ehvi_finish(const EhviArgs&, long long, bool, double h) { return h; }
+__device__ __forceinline__ double ehvi_finish(const EhviConArgs& c, long long i, bool valid, double h) {
+  const double p = ehvi_pof_product(c, i, valid);
+  if (valid && c.pof) bo_out_store(c.pof + i, p);
+  return h * p;
+}
+
 template <int M>
 __device__ __forceinline__ bool ehvi_load(const EhviArgs& a, long long i, bool valid, double* mu, double* sg,
                                           double* rs) {

@@ -462,6 +462,43 @@ int bo_expected_hypervolume_improvement(double* acq, const double* mu, const dou
                                         const int32_t* n_edges, const int32_t* box_idx,
                                         int32_t form, void* stream);
 
+/* Outcome constraints: the feasibility-weighted EHVI (Gardner et al. 2014 and Gelbart et al. 2014
+ * for EI, Feliot et al. 2017 for the hypervolume form).  NOT in the reference: parity is unpinned
+ * by it.  The outputs are ordered objectives first, n_out = n_obj + n_con with 1 <= n_obj <= 4 and
+ * n_out <= BO_MAX_OBJ; every output has its own independent GP.  Constraint j has bounds
+ * lo_j <= hi_j, either infinite on its own side (lo = -inf, hi = +inf), neither NaN; a point is
+ * feasible iff lo_j <= g_j <= hi_j for every j.  With the constraint rows of mu / var,
+ * sigma = sqrt(|var|) (the UCB's and the EHVI's convention), za = (lo - mu) / sigma and
+ * zb = (hi - mu) / sigma:
+ *   P_j = Phi(zb) - Phi(za)       the probability that constraint j holds
+ *   acq = EHVI(objective rows; the boxes of the FEASIBLE front above the reference point) prod_j P_j
+ * P_j keeps its relative accuracy in both tails (when no candidate is likely feasible the order of
+ * 1e-30 against 1e-40 is all a selection has): it is a difference of positive tail terms,
+ * Q(z) = erfc(z / sqrt 2) / 2,
+ *   Q(za) - Q(zb) for za > 0,   Q(-zb) - Q(-za) for zb < 0,   (1 - Q(zb)) - Q(-za) otherwise.
+ * LIMITS: sigma = 0 gives 1 when lo <= mu <= hi (the bounds included), else 0; the bounds
+ * (-inf, +inf) give exactly 1; NaN in any mu or var of any row, objective or constraint, gives
+ * acq = NaN (selected first, as for the EHVI).
+ * ROUNDING RULE: with E the value bo_expected_hypervolume_improvement gives for the objective rows
+ * (the same bits, rule for the form and box order) and P = ((P_0 P_1) P_2) ... in f64, left to
+ * right, acq = fl(E P); the table form and the direct form give the same bits.
+ *
+ * bo_constrained_ehvi: mu / var are device [n_obj + n_con][ld]; con_lo / con_hi are HOST [n_con]
+ * (passed to the kernel by value); boxes, the tables and `form` are those of
+ * bo_expected_hypervolume_improvement over the n_obj objectives (the table holds objective edges
+ * only, so the admission rule and auto's rule are unchanged).  pof_out (optional, device [n])
+ * receives P (NaN where a constraint row holds NaN).  n_con = 0 is the plain scan with the same
+ * bits, and pof_out is then 1.  Every argument is checked before the device is touched: BO_ERR_ARG
+ * for lo > hi, a NaN bound, lo = +inf, hi = -inf, n_obj outside 1..4, n_con < 0,
+ * n_obj + n_con > BO_MAX_OBJ, or con_lo / con_hi NULL with n_con > 0; otherwise the statuses of
+ * bo_expected_hypervolume_improvement.  Asynchronous on `stream`, capturable in a HIP graph,
+ * deterministic. */
+int bo_constrained_ehvi(double* acq, double* pof_out, const double* mu, const double* var,
+                        int64_t ld, int64_t n, int32_t n_obj, int32_t n_con, const double* con_lo,
+                        const double* con_hi, const double* boxes, int64_t n_boxes,
+                        const double* edges, const int32_t* n_edges, const int32_t* box_idx,
+                        int32_t form, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Kriging-believer batches for the EHVI (Ginsbourger, Le Riche & Carraro 2010; opt-in
  * batch_strategy "kb").  NOT in the reference.  The q best values of one EHVI array are q
