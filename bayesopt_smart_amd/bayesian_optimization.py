@@ -43,7 +43,7 @@ def _check_acquisition(acquisition):
         raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi' or 'ehvi')")
 from .config import (DEFAULT_BATCH_SIZE, DEFAULT_BETA, DEFAULT_INITIAL_SAMPLES,
                      DEFAULT_LENGTH_SCALE, DEFAULT_PRIOR_MEAN, DEFAULT_PRIOR_VARIANCE,
-                     resolve_float_type)
+                     check_fit_method, resolve_float_type)
 from .device import F64, require_device
 from .pareto import compute_pareto_front, print_pareto_analysis
 from .predict import CandidateSet, predict_acquire
@@ -131,10 +131,11 @@ class DeviceBackend:
     the f32 matrix-core kernel (mode "fp32") with the variance floor 1e-6."""
 
     def __init__(self, cands, n_obj, total_samples, device=None, buffers=None, group=None, float_type=None,
-                 ts_features=1024, ts_seed=0):
+                 ts_features=1024, ts_seed=0, fit_method="powell"):
         from .distributed import shard_range
         self.dev = require_device(device)
         self.float_type = resolve_float_type(float_type)
+        self.fit_method = check_fit_method(fit_method)
         self.mode = "fp32" if self.float_type == np.float32 else "auto"
         self.cands = cands
         self.group = group
@@ -156,8 +157,11 @@ class DeviceBackend:
         """Returns (Powell's OptimizeResult, fitted device state, time after the Powell fit)."""
         xd = torch.as_tensor(np.ascontiguousarray(x_vector[:n], dtype=np.float64), device=self.dev)
         yd = torch.as_tensor(np.ascontiguousarray(y_vector[:n], dtype=np.float64), device=self.dev)
+        # the default is the reference's fit, called as before; "lbfgs" names itself
+        method = {} if self.fit_method == "powell" else {"method": self.fit_method}
         optimized = K.optimize_hyperparams_mll(xd, yd, self.bufs.kernel_matrices, prior_mean,
-                                               prior_variance, length_scales, n, float_type=self.float_type)
+                                               prior_variance, length_scales, n, float_type=self.float_type,
+                                               **method)
         _broadcast_np(length_scales, self.group, self.dev)
         _broadcast_np(prior_variance, self.group, self.dev)
         t1 = time.perf_counter()
@@ -350,7 +354,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
              callbacks: Optional[List[Callable]] = None, *,
              acquisition: str = "sum_ucb", group=None, backend=None,
              float_type=None, batch_strategy: str = "top", ts_features: int = 1024,
-             ts_seed: int = 0, constraint_bounds=None) -> Tuple[np.ndarray, np.ndarray, int]:
+             ts_seed: int = 0, constraint_bounds=None, fit_method: str = "powell") -> Tuple[np.ndarray, np.ndarray, int]:
     """bayesian_optimization.py:51-247 with the reference's argument list.
 
     `kernel_matrices` and the posterior arrays may be HIP tensors (in place) or numpy arrays;
@@ -379,6 +383,9 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     rows, reference_point has one coordinate per objective -- and the acquisition is the EHVI over
     the front of the feasible evaluated points times the probability of feasibility
     (DeviceBackend.select).
+    `fit_method` "lbfgs" fits the length scales by L-BFGS-B over log ls with the device's analytic
+    MLL gradient (kernels.optimize_hyperparams_mll, method="lbfgs": prior_variance stays as given);
+    "powell", the default, is the reference's fit.  It is the backend's when `backend` is given.
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -412,7 +419,7 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         bufs.ucb = dev_buf(ucb, (n_obj, cnt))
         bufs.acquisition_values = dev_buf(acquisition_values, (cnt,))
         backend = DeviceBackend(cands, n_obj, total_samples, dev, bufs, group, float_type=float_type,
-                                ts_features=ts_features, ts_seed=ts_seed)
+                                ts_features=ts_features, ts_seed=ts_seed, fit_method=fit_method)
     cands, rank, world = backend.cands, backend.rank, backend.world
     gather = bool(callbacks)
     bgroup = getattr(backend, "group", group)
@@ -554,10 +561,11 @@ def _check_constraints(n_obj, n_con, constraint_bounds, acquisition, batch_strat
 
 
 def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", batch_strategy="top", group=None,
-                  n_constraints=0, constraint_bounds=None):
+                  n_constraints=0, constraint_bounds=None, fit_method="powell"):
     """Fail in the constructor -- before any objective evaluation -- on shapes the device path
     cannot run (the reference would hit them only mid-loop, if at all).  n_obj counts the
     objectives; the n_constraints outcome constraints are further outputs."""
+    check_fit_method(fit_method)
     _check_constraints(n_obj, n_constraints, constraint_bounds, acquisition, batch_strategy)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, group)
     if not 1 <= n_obj <= _lib.MAX_OBJ:
@@ -613,7 +621,11 @@ class BayesianOptimization:
     n_objectives + n_constraints columns and prior_mean / prior_variance / length_scales / betas
     that length, reference_point has length n_objectives; the acquisition is the EHVI over the
     front of the feasible evaluated points times the probability of feasibility, and
-    pareto_analysis reports the feasible front over the objective columns).
+    pareto_analysis reports the feasible front over the objective columns), and ``fit_method``
+    ("powell", the reference's fit; or "lbfgs": L-BFGS-B over log(length scale) with the device's
+    analytic MLL gradient, kernels.optimize_hyperparams_mll -- every output's GP is fitted the same
+    way, prior_variance stays as computed from the initial design, and rank 0's result is broadcast
+    as the Powell fit's is).
     With several ranks, each holds its shard of the posterior arrays, the initial design is drawn
     and evaluated on rank 0 (every rank draws the same RNG numbers, so the RNG stays in step) and
     broadcast, and the loop runs as `optimize` describes.
@@ -665,8 +677,9 @@ class BayesianOptimization:
         self.ts_seed = kwargs.get("ts_seed", 0)
         if not 1 <= self.ts_features <= _lib.TS_MAX_FEATURES:
             raise ValueError(f"ts_features must be in [1, {_lib.TS_MAX_FEATURES}] (got {self.ts_features})")
+        self.fit_method = kwargs.get("fit_method", "powell")
         _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
-                      self.batch_strategy, self.group, self.n_constraints, self.constraint_bounds)
+                      self.batch_strategy, self.group, self.n_constraints, self.constraint_bounds, self.fit_method)
         self.reference_point = np.array(kwargs.get("reference_point", [0.0] * n_objectives), dtype=ft)
         if self.constraint_bounds is not None:
             self.constraint_bounds = check_constraint_bounds(self.constraint_bounds, self.n_constraints)
@@ -681,7 +694,7 @@ class BayesianOptimization:
         self.y_vector = np.zeros((self.total_samples, n_out), dtype=ft)
         self._backend = DeviceBackend(self.candidates, n_out, self.total_samples, self.device,
                                       group=self.group, float_type=ft, ts_features=self.ts_features,
-                                      ts_seed=self.ts_seed)
+                                      ts_seed=self.ts_seed, fit_method=self.fit_method)
         self._buffers = self._backend.bufs
         self.k_star = None   # never materialised (the reference allocates n_obj x T x M here)
         rank, world = _world(self.group)
@@ -738,7 +751,7 @@ class BayesianOptimization:
             bounds=self.bounds, callbacks=self.callbacks if self.callbacks else None,
             acquisition=self.acquisition, group=self.group, backend=self._backend,
             float_type=self.float_type, batch_strategy=self.batch_strategy, ts_features=self.ts_features,
-            ts_seed=self.ts_seed, constraint_bounds=self.constraint_bounds)
+            ts_seed=self.ts_seed, constraint_bounds=self.constraint_bounds, fit_method=self.fit_method)
 
     def pareto_analysis(self) -> np.ndarray:
         """bayesian_optimization.py:465-488.  With outcome constraints: the front of the feasible

@@ -55,4 +55,14 @@ HYPERPARAM_FTOL = 1e-4
 HYPERPARAM_MAXITER = 1000
 HYPERPARAM_MIN_BOUND = 1e-5
 
+# the fit's methods: "powell" is the reference's (HYPERPARAM_METHOD above; COBYLA in the float32
+# branch), "lbfgs" scipy's L-BFGS-B over log(length scale) with the device's analytic gradient
+FIT_METHODS = ("powell", "lbfgs")
+
+
+def check_fit_method(method):
+    if method not in FIT_METHODS:
+        raise ValueError(f"unknown fit method {method!r} (expected 'powell' or 'lbfgs')")
+    return method
+
 DEFAULT_PLOT_ENABLED = True

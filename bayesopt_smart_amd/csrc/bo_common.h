@@ -489,6 +489,12 @@ int bo_lu_max_n();
 int bo_lu_inverse(double* const* out, const double* const* km, int n_lu, int64_t ld, int64_t n, double jitter,
                   void* ws, size_t ws_bytes, hipStream_t s);
 
+// invert_k's Cholesky path alone (bo_fit.hip: the factorisation, with its Newton step when `refine`;
+// no LU or Gauss-Jordan), called by bo_compute_mll_grad (bo_mll_grad.hip); workspace as bo_invert_k,
+// fail[o] host [n_obj]
+int bo_fit_cholesky_inverse(double* out, const double* km, int64_t ld, int32_t n_obj, int64_t n, double jitter,
+                            bool refine, int32_t* fail, void* ws, size_t ws_bytes, hipStream_t s);
+
 // the lean final merge of sorted top-q lists (bo_select.hip; q <= 4, n_lists <= 1024), used after
 // the fused kernel; false when it does not apply
 bool bo_launch_rounds_merge(const TopEntry* lists, long long n_lists, int q, double* out_v, int64_t* out_i,

@@ -1542,12 +1542,13 @@ bool refine_enabled() { return !bo_env_is(BO_ENV_ONCE("BO_INV_REFINE"), "0"); }
 
 // The Cholesky path's result: -C mirrored into X (the dead first columns of each objective's
 // augmented matrix), then one Newton step X + X (I - (K + jitter I) X) into `out`
-// (inv_refine_kernel).  Objectives whose factorisation failed are skipped on the device.
+// (inv_refine_kernel); !refine: -C straight into `out`.  Objectives whose factorisation failed are
+// skipped on the device.
 int inv_finish(double* out, double* A, const Geo& g, const double* km, long long ld, double jitter,
-               const int* status, hipStream_t s) {
+               const int* status, bool refine, hipStream_t s) {
   const unsigned nt = (unsigned)g.nbt;
   const long long n = g.n;
-  if (!refine_enabled()) {
+  if (!refine) {
     hipLaunchKernelGGL(inv_extract_kernel, dim3(nt, nt, g.n_obj), dim3(256), 0, s, out, n * n, A, g, status);
     return hipGetLastError() == hipSuccess ? BO_OK : BO_ERR_HIP;
   }
@@ -1581,7 +1582,7 @@ void* pinned(size_t bytes) {
 
 // The inverse's Cholesky attempt for all objectives: factorise (fit_run), finish, read the
 // statuses back.  fail[o] != 0: objective o goes on to the LU path.
-int inv_cholesky(double* out, const FitJob& j, int* fail, hipStream_t s) {
+int inv_cholesky(double* out, const FitJob& j, int* fail, bool refine, hipStream_t s) {
   const Geo& g = j.g;
   int* hstat = (int*)pinned(sizeof(int) * kInvStatWords);
   if (!hstat) return BO_ERR_HIP;
@@ -1590,7 +1591,7 @@ int inv_cholesky(double* out, const FitJob& j, int* fail, hipStream_t s) {
     return BO_OK;
   };
   auto wait = [&](bool persistent, bool& aborted) -> int {
-    const int st = inv_finish(out, j.A, g, j.km, j.ld, j.p.jitter, j.status, s);
+    const int st = inv_finish(out, j.A, g, j.km, j.ld, j.p.jitter, j.status, refine, s);
     if (st != BO_OK) return st;
     BO_CHECK_HIP(hipMemcpyAsync(hstat, j.status, sizeof(int) * (persistent ? kInvStatWords : g.n_obj),
                                 hipMemcpyDeviceToHost, s));
@@ -1671,6 +1672,34 @@ int gj_inverse(double* out, const double* km, long long ld, long long n, int o, 
 
 }  // namespace
 
+// bo_invert_k's Cholesky path alone (the factorisation, with its Newton step when `refine`; no LU
+// or Gauss-Jordan after it), for bo_compute_mll_grad (bo_mll_grad.hip).  Arguments and workspace as
+// bo_invert_k_jitter; fail[o] != 0 (host, [n_obj]): objective o's factorisation met a non-positive
+// pivot or its matrix is not symmetric, and out[o] is not written.
+int bo_fit_cholesky_inverse(double* out, const double* km, int64_t ld, int32_t n_obj, int64_t n, double jitter,
+                            bool refine, int32_t* fail, void* ws, size_t ws_bytes, hipStream_t s) {
+  if (!out || !km || !fail || n_obj < 1 || n_obj > BO_MAX_OBJ || n < 1 || ld < n) return BO_ERR_ARG;
+  if (n > (1 << 15)) return BO_ERR_UNSUPPORTED;
+  if (!ws || ws_bytes < bo_invert_k_workspace_size(n_obj, n)) return BO_ERR_WORKSPACE;
+  char* w = (char*)ws;
+  FitJob j;
+  memset(&j, 0, sizeof(j));
+  j.g = make_geo((int)n, n_obj, true);
+  const InvLayout L = inv_layout(j.g);
+  j.A = (double*)(w + L.A);
+  j.km = km;
+  j.ld = ld;
+  j.p.jitter = jitter;
+  j.status = (int*)(w + L.status);
+  j.flags = (int*)(w + L.flags);
+  j.habort = j.status + kInvStatAbort;
+  int f[BO_MAX_OBJ];
+  const int st = inv_cholesky(out, j, f, refine, s);
+  if (st != BO_OK) return st;
+  for (int o = 0; o < n_obj; ++o) fail[o] = f[o];
+  return BO_OK;
+}
+
 extern "C" {
 
 size_t bo_invert_k_workspace_size(int32_t n_obj, int64_t n) {
@@ -1713,7 +1742,7 @@ int bo_invert_k_ex(double* out, const double* km, int64_t ld, int32_t n_obj, int
     fail[o] = 1;
     if (all_lu && lu_hint[o] == 0) all_lu = false;
   }
-  int st = all_lu ? BO_OK : inv_cholesky(out, j, fail, s);
+  int st = all_lu ? BO_OK : inv_cholesky(out, j, fail, refine_enabled(), s);
   if (st != BO_OK) return st;
   // path bookkeeping: 0 Cholesky, 1 LU, 2 Gauss-Jordan (what the LU batch left)
   int path[BO_MAX_OBJ];

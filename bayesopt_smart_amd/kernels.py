@@ -24,8 +24,8 @@ from . import _lib
 from scipy.optimize import OptimizeResult
 
 from .config import (HYPERPARAM_FTOL, HYPERPARAM_MAXITER, HYPERPARAM_METHOD,
-                     HYPERPARAM_MIN_BOUND, HYPERPARAM_XTOL, NUMBA_FLOAT_TYPE, precision_constants,
-                     resolve_float_type)
+                     HYPERPARAM_MIN_BOUND, HYPERPARAM_XTOL, NUMBA_FLOAT_TYPE, check_fit_method,
+                     precision_constants, resolve_float_type)
 from .device import F64, Workspace, require_device, stream_handle
 
 
@@ -201,6 +201,75 @@ def _mll_terms(xd, yd, km, prior_mean, prior_variance, length_scales, n, objs, j
     return {o0 + i: out[i] for i in range(cnt)}
 
 
+def _mll_grad_call(xd, yd, km, pm, pv, ls, n, jitter, ws=None):
+    """bo_compute_mll_grad on device arrays: (terms, grad_log_ls) as numpy arrays [n_obj]."""
+    lib = _lib.load()
+    n_obj, ld = km.shape[0], km.shape[-1]
+    dev = km.device
+    if ws is None:
+        ws = Workspace.get(lib.bo_compute_mll_grad_workspace_size(n_obj, n), dev)
+    val = (C.c_double * n_obj)()
+    grad = (C.c_double * n_obj)()
+    st = lib.bo_compute_mll_grad(val, grad, xd.data_ptr(), xd.shape[1], yd.data_ptr(), yd.stride(0), km.data_ptr(),
+                                 ld, n_obj, _host_vec(pm, n_obj), _host_vec(pv, n_obj), _host_vec(ls, n_obj), n,
+                                 jitter, ws.data_ptr(), ws.numel(), stream_handle(dev))
+    _lib.check(st, "bo_compute_mll_grad")
+    return np.array(val[:n_obj], dtype=np.float64), np.array(grad[:n_obj], dtype=np.float64)
+
+
+def compute_mll_grad(x_vector, y_vector, kernel_matrix, prior_mean, prior_variance, length_scales,
+                     current_eval, *, float_type=None):
+    """The per-objective MLL terms (compute_mll is their sum in objective order; the bits of
+    bo_compute_mll_each) and their analytic gradients in log(length scale), both numpy [n_obj]:
+
+        grad_log_ls[o] = d MLL_o / d log ls_o = 1/2 sum_ij (alpha_i alpha_j - C^-1_ij) e_ij r2_ij / ls_o^2
+
+    with C = e + CHOLESKY_JITTER I and alpha = C^-1 yc (yc: y - pm over its population std); divide by
+    ls_o for the derivative in ls_o.  The derivative in prior_variance is exactly 0 (the MLL factors the
+    correlation matrix) and is not returned.  kernel_matrix is rebuilt in place as compute_mll does.
+    Raises numpy.linalg.LinAlgError when the matrix is not positive definite."""
+    dev = _dev_of(kernel_matrix, x_vector, y_vector)
+    km = _Arg(kernel_matrix, dev, write=True)
+    x = _Arg(x_vector, dev)
+    y = _Arg(y_vector, dev)
+    try:
+        return _mll_grad_call(x.t, y.t, km.t, prior_mean, prior_variance, length_scales, int(current_eval),
+                              precision_constants(float_type)[1])
+    finally:
+        km.finish()
+
+
+def _lbfgs_fit(xd, yd, km, pm, prior_variance, length_scales, pv0, ls0, n_obj, n, chol_jitter):
+    """optimize_hyperparams_mll's method="lbfgs": scipy's L-BFGS-B over t = log ls around
+    bo_compute_mll_grad, one call over all objectives per evaluation."""
+    lib = _lib.load()
+    pv = np.array(pv0, dtype=np.float64)[:n_obj].copy()
+    ws = Workspace.get(lib.bo_compute_mll_grad_workspace_size(n_obj, n), km.t.device)
+    calls = [0]
+
+    def objective(t):
+        calls[0] += 1
+        val, grad = _mll_grad_call(xd, yd, km.t, pm, pv, np.exp(t), n, chol_jitter, ws)
+        tot = 0.0
+        for o in range(n_obj):                  # compute_mll's sum over the objectives, in order
+            tot += val[o]
+        return -tot, -grad
+
+    t0 = np.log(np.array(ls0, dtype=np.float64)[:n_obj])
+    res = minimize(objective, t0, method="L-BFGS-B", jac=True,
+                   bounds=[(float(np.log(HYPERPARAM_MIN_BOUND)), None)] * n_obj,
+                   options={"ftol": HYPERPARAM_FTOL, "maxiter": HYPERPARAM_MAXITER})
+    ls = np.exp(res.x)
+    update_k(km.t, xd, 0, n, pv, ls)            # kernel_matrix: the Gram of the result
+    km.finish()
+    _assign(length_scales, ls)
+    _assign(prior_variance, pv)                  # the caller's values, bit for bit
+    msg = res.message.decode() if isinstance(res.message, bytes) else str(res.message)
+    return OptimizeResult(x=np.concatenate([ls, pv]), fun=float(res.fun), jac=np.array(res.jac, dtype=np.float64),
+                          nfev=int(res.nfev), nit=int(res.nit), device_calls=calls[0], status=int(res.status),
+                          success=bool(res.success), message=msg)
+
+
 _POWELL_MESSAGES = {0: "Optimization terminated successfully.",
                     1: "Maximum number of function evaluations has been exceeded.",
                     2: "Maximum number of iterations has been exceeded.",
@@ -249,7 +318,7 @@ def powell_minimize(fun, x0, bounds, xtol=1e-4, ftol=1e-4, maxiter=None, maxfev=
 
 def optimize_hyperparams_mll(x_vector, y_vector, kernel_matrix, prior_mean, prior_variance,
                              length_scales, current_eval, memo=True, *, float_type=None, driver="native",
-                             numpy_trig=True):
+                             numpy_trig=True, method=None):
     """numba_kernels.py:238-321 — maximise the device MLL over [ls..., var...] (bounds >= 1e-5);
     updates length_scales and prior_variance in place, returns the OptimizeResult.  The training
     arrays are staged on the device once for all ~100-300 MLL evaluations.
@@ -269,7 +338,20 @@ def optimize_hyperparams_mll(x_vector, y_vector, kernel_matrix, prior_mean, prio
     like np.sum (:235).  The returned values are bit-identical to recomputing every term (the same
     device arithmetic), so Powell's path is unchanged; evaluations that move only pv need no
     device call (about half of them).  kernel_matrix ends as the reference leaves it: the Gram of
-    the last evaluated hyper-parameters."""
+    the last evaluated hyper-parameters.
+
+    `method`: None or "powell" is everything above, unchanged (None keeps the float32 branch's
+    COBYLA).  "lbfgs" runs scipy's L-BFGS-B (jac=True) over t = log ls from log(length_scales),
+    lower bound log(HYPERPARAM_MIN_BOUND), no upper bound, ftol = HYPERPARAM_FTOL, maxiter =
+    HYPERPARAM_MAXITER; each evaluation is one compute_mll_grad call over all objectives, the
+    training arrays staged once.  prior_variance is returned UNCHANGED, bit for bit: the MLL
+    factors the correlation matrix, so its derivative in pv is exactly zero and there is nothing to
+    fit (the pv a Powell fit returns is a by-product of its line searches along that flat
+    direction).  length_scales is updated in place, kernel_matrix ends as update_k's Gram of the
+    final (ls, pv), and the OptimizeResult carries x = [ls..., pv...] (the Powell layout), fun, jac
+    (in log ls), nfev, nit, device_calls and message.  A LinAlgError from an evaluation propagates."""
+    if method is not None:
+        check_fit_method(method)
     ft = resolve_float_type(float_type)
     _, chol_jitter, _ = precision_constants(ft)
     dev = _dev_of(kernel_matrix, x_vector, y_vector)
@@ -283,6 +365,8 @@ def optimize_hyperparams_mll(x_vector, y_vector, kernel_matrix, prior_mean, prio
     pm = np.asarray(prior_mean.cpu().numpy() if isinstance(prior_mean, torch.Tensor) else prior_mean,
                     dtype=np.float64)
     n = int(current_eval)
+    if method == "lbfgs":
+        return _lbfgs_fit(xd, yd, km, pm, prior_variance, length_scales, pv0, ls0, n_obj, n, chol_jitter)
     lib = _lib.load()
     if ft == np.float64 and driver == "native" and memo and HYPERPARAM_METHOD == "Powell":
         ls_io = np.array(ls0, dtype=np.float64)

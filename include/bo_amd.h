@@ -650,6 +650,32 @@ int bo_compute_mll_each_jitter(double* mll_obj, const double* x, int32_t dim, co
                                void* workspace, size_t workspace_bytes, void* stream);
 size_t bo_compute_mll_workspace_size(int32_t n_obj, int64_t n);
 
+/* The per-objective MLL terms and their analytic gradients in the logarithm of the length scale
+ * (additive in ABI 5).  Per objective o, with C = e + jitter I, e_ij = exp(-r2_ij / (2 ls^2)),
+ * yc = (y - pm) / std (the MLL's own standardisation: population std about its own mean, left
+ * unscaled when that std is 0) and alpha = C^-1 yc:
+ *
+ *   mll_obj[o]     (host, [n_obj])  the bits bo_compute_mll_each_jitter returns for the same
+ *                  arguments (it is that call: same factorisation path and schedule; the side
+ *                  effect is the same too, kernel_matrix ends as pv e);
+ *   grad_log_ls[o] (host, [n_obj])  d MLL_o / d log ls_o
+ *                  = 1/2 sum_ij (alpha_i alpha_j - C^-1_ij) e_ij r2_ij / ls^2;
+ *                  the derivative in ls_o is this value divided by ls_o.
+ *
+ * The MLL does not depend on prior_var (the correlation matrix is factored), so its derivative in
+ * prior_var is exactly 0 and is not returned.  C^-1 is the augmented-Cholesky inverse (bo_invert_k's
+ * first path, without its Newton step, which measured three orders of magnitude less accurate for
+ * this sum) of a pv-free copy of e built into the workspace; there is no LU or Gauss-Jordan fallback: BO_ERR_NOT_PD when the value's factorisation, or the inverse's, meets a
+ * non-positive pivot (the value's error is returned before anything else runs).  The reduction
+ * uses no floating-point atomics: per-tile partial sums are added in tile order, so two calls
+ * return the same bits.  Limits: n_obj <= BO_MAX_OBJ, n <= 2^15 (the inverse's range); the size
+ * function returns 0 outside them.  No allocation in the call; synchronous. */
+int bo_compute_mll_grad(double* mll_obj, double* grad_log_ls, const double* x, int32_t dim, const double* y,
+                        int64_t ld_y, double* kernel_matrix, int64_t ld, int32_t n_obj,
+                        const double* prior_mean, const double* prior_var, const double* length_scale,
+                        int64_t n, double jitter, void* workspace, size_t workspace_bytes, void* stream);
+size_t bo_compute_mll_grad_workspace_size(int32_t n_obj, int64_t n);
+
 /* ------------------------------------------------------------------------------------
  * The fit's driver, native (HOST code calling the device MLL): scipy.optimize.minimize(
  * method="Powell", bounds=...) as optimize_hyperparams_mll calls it (numba_kernels.py:238-321,
