@@ -920,3 +920,118 @@ def select_batch_ts(x_train, y_train, kinv, cands, prior_mean, prior_variance, l
     if return_details:
         return {"picks": picks, "paths": paths, "lists": lists, "vals": vals}
     return picks[picks >= 0]
+
+
+# ------------------------------------------------- max-value entropy search (MESMO)
+def path_maxima(paths, prior_mean, prior_variance, group=None):
+    """The per-draw maxima of posterior draws in objective units (bo_path_maxima):
+    ystar[s, k] = fl(prior_mean[k] + sqrt(prior_variance[k]) * max_c paths[s, k, c]), one rounding, NaN
+    entries ignored (an all-NaN or empty row gives NaN).  paths: sample_paths' device tensor
+    [S, n_obj, count] (a view with a larger row stride is taken as it is).  With collectives on, the
+    ranks' maxima are combined by one all_reduce(MAX) -- the max is exact and the map monotone, so
+    every rank then holds the bits of the unsharded call; the collective's tensor is on the device
+    for RCCL and a host copy for gloo.  Returns a device tensor [S, n_obj].  NOT in the reference."""
+    if not isinstance(paths, torch.Tensor) or paths.device.type != "cuda" or paths.dtype != F64 or paths.dim() != 3:
+        raise ValueError("paths must be a float64 HIP tensor [S, n_obj, count]")
+    n_s, n_obj, count = paths.shape
+    if not 1 <= n_s <= _lib.MAX_TOPQ or not 1 <= n_obj <= _lib.MAX_OBJ:
+        raise ValueError(f"path_maxima handles 1 <= S <= {_lib.MAX_TOPQ} and 1 <= n_obj <= {_lib.MAX_OBJ}")
+    # the row stride of the [S n_obj][ld] layout the paths are a view of (a dimension of size 1 has none)
+    ld = paths.stride(1) if n_obj > 1 else (paths.stride(0) if n_s > 1 else count)
+    if (count > 1 and paths.stride(2) != 1) or (n_s > 1 and paths.stride(0) != n_obj * ld) or ld < count:
+        paths = paths.contiguous()
+        ld = count
+    dev = paths.device
+    lib = _lib.load()
+    ystar = torch.empty((n_s, n_obj), dtype=F64, device=dev)
+    ws = Workspace.get(lib.bo_path_maxima_workspace_size(count, n_s * n_obj), dev)
+    scale = np.sqrt(np.asarray(prior_variance, dtype=np.float64))
+    _lib.check(lib.bo_path_maxima(ystar.data_ptr(), paths.data_ptr(), ld, count, n_s, n_obj,
+                                  _host_vec(prior_mean, n_obj), _host_vec(scale, n_obj), ws.data_ptr(), ws.numel(),
+                                  stream_handle(dev)), "bo_path_maxima")
+    from .distributed import collectives_on
+    if collectives_on(group):
+        import torch.distributed as dist
+        if dist.get_backend(group) == "nccl":
+            dist.all_reduce(ystar, op=dist.ReduceOp.MAX, group=group)
+        else:                                       # gloo: the collective on a host copy
+            h = ystar.cpu()
+            dist.all_reduce(h, op=dist.ReduceOp.MAX, group=group)
+            ystar.copy_(h)
+    return ystar
+
+
+def max_value_entropy(mu, var, ystar, out=None):
+    """The max-value entropy search acquisition of every candidate (bo_max_value_entropy;
+    include/bo_amd.h states the quantity, its limits and its rounding rule):
+    acq = (1/S) sum_s sum_k g((ystar[s, k] - mu[k]) / sqrt(|var[k]|)),
+    g(x) = x phi(x) / (2 Phi(x)) - ln Phi(x).  mu / var: the predict's mu_objectives /
+    variance_objectives in objective units, [n_obj, M] with 1 <= n_obj <= 8, numpy or HIP tensors;
+    ystar: [S, n_obj] sampled maxima (path_maxima), 1 <= S <= BO_MAX_TOPQ.  NOT in the reference.
+    Returns acq ([M], a device tensor, or numpy for numpy `mu`); written into `out` when given."""
+    dev = _dev_of(out, mu, ystar)
+    m = _Arg(mu, dev)
+    v = _Arg(var, dev)
+    if m.t.dim() != 2 or v.t.shape != m.t.shape:
+        raise ValueError("mu / var must both be [n_obj, M]")
+    n_obj, n = m.t.shape
+    ys = _Arg(ystar, dev)
+    if ys.t.dim() != 2 or ys.t.shape[1] != n_obj:
+        raise ValueError(f"ystar must be [S, n_obj] with n_obj = {n_obj}")
+    n_s = ys.t.shape[0]
+    if not 1 <= n_s <= _lib.MAX_TOPQ or not 1 <= n_obj <= _lib.MAX_OBJ:
+        raise ValueError(f"max_value_entropy handles 1 <= S <= {_lib.MAX_TOPQ} and 1 <= n_obj <= {_lib.MAX_OBJ}")
+    acq = _Arg(out, dev, write=True) if out is not None else None
+    dst = acq.t if acq is not None else torch.empty(n, dtype=F64, device=dev)
+    if dst.numel() != n:
+        raise ValueError(f"out holds {dst.numel()} values for {n} candidates")
+    _lib.check(_lib.load().bo_max_value_entropy(dst.data_ptr(), m.ptr, v.ptr, n, n, n_obj, ys.ptr, n_s,
+                                                stream_handle(dev)), "bo_max_value_entropy")
+    if acq is not None:
+        acq.finish()
+        return out
+    return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
+
+
+def update_max_value_entropy(acquisition_values, mu_objectives, variance_objectives, ystar):
+    """The acquisition update of the loop (bayesian_optimization.py:195-199) as the max-value entropy
+    search acquisition over the sampled maxima `ystar` ([S, n_obj], path_maxima); in place into
+    `acquisition_values`."""
+    max_value_entropy(mu_objectives, variance_objectives, ystar, out=acquisition_values)
+
+
+def mes_select_indices(acquisition_values, mu_objectives, variance_objectives, x_train, y_train, kinv, cands,
+                       prior_mean, prior_variance, length_scales, draws, evaluated_points, batch_size, offset=0,
+                       return_record=False, mask=None, float_type=None, jitter=None, group=None, select=True):
+    """The max-value entropy search acquisition and its batch selection over one shard, shaped like
+    ehvi_select_indices: the posterior draws over the shard (sample_paths with `draws`, as
+    thompson_draws returns them -- every rank the same), their maxima (path_maxima: over ALL
+    candidates, the ranks' shards combined by one all_reduce(MAX) when collectives are on), the scan
+    into acquisition_values (device, [count]: the candidates [offset, offset + count) of `cands`,
+    from the predict's mu_objectives / variance_objectives over that shard), then
+    bo_select_topq_masked over the shard's ExclusionMask (`mask`, updated here with
+    evaluated_points; without one a mask is built for the call).  batch_size <= BO_MAX_TOPQ.
+    Returns the global indices of the shard's best batch_size candidates not equal to an evaluated
+    point (select_next_batch's order, NaN first) -- or, `return_record`, the device record block
+    [2 batch_size] for the multi-rank exchange.  `select` False: the scan only (returns None)."""
+    if select and batch_size > _lib.MAX_TOPQ:
+        raise ValueError(f"mes_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
+    dev = _dev_of(acquisition_values, mu_objectives)
+    acq = _Arg(acquisition_values, dev, write=True)
+    n = acq.t.numel()
+    paths = sample_paths(x_train, y_train, kinv, cands, prior_mean, prior_variance, length_scales, draws,
+                         offset=offset, count=n, float_type=float_type, jitter=jitter, device=dev)
+    ystar = path_maxima(paths, prior_mean, prior_variance, group=group)
+    max_value_entropy(mu_objectives, variance_objectives, ystar, out=acq.t)
+    if not select:
+        acq.finish()
+        return None
+    mask = _shard_mask(mask, cands, offset, n, dev, evaluated_points, "mes_select_indices")
+    rec = torch.empty(2 * batch_size, dtype=F64, device=dev)
+    lib = _lib.load()
+    ws = Workspace.get(lib.bo_select_topq_workspace_size(n, batch_size), dev)
+    _lib.check(lib.bo_select_topq_masked(acq.ptr, n, offset, mask.ptr, batch_size, rec.data_ptr(),
+                                         rec.data_ptr() + 8 * batch_size, ws.data_ptr(), ws.numel(),
+                                         stream_handle(dev)), "bo_select_topq_masked")
+    acq.finish()
+    return rec if return_record else _record_indices(rec, batch_size)

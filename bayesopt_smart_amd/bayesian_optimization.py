@@ -30,17 +30,19 @@ import torch
 
 from . import kernels as K
 from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, _record_indices, check_constraint_bounds,
-                          ehvi_select_indices, feasible_rows, hvi_select_indices, select_batch_bucb,
+                          ehvi_select_indices, feasible_rows, hvi_select_indices, mes_select_indices,
+                          select_batch_bucb,
                           select_batch_kb, select_batch_ts,
                           select_indices, thompson_draws,
                           update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
 
-ACQUISITIONS = ("sum_ucb", "hvi", "ehvi")
+ACQUISITIONS = ("sum_ucb", "hvi", "ehvi", "mes")
+DEFAULT_MES_SAMPLES = 8
 
 
 def _check_acquisition(acquisition):
     if acquisition not in ACQUISITIONS:
-        raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi' or 'ehvi')")
+        raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi', 'ehvi' or 'mes')")
 from .config import (DEFAULT_BATCH_SIZE, DEFAULT_BETA, DEFAULT_INITIAL_SAMPLES,
                      DEFAULT_LENGTH_SCALE, DEFAULT_PRIOR_MEAN, DEFAULT_PRIOR_VARIANCE,
                      check_fit_method, resolve_float_type)
@@ -131,7 +133,7 @@ class DeviceBackend:
     the f32 matrix-core kernel (mode "fp32") with the variance floor 1e-6."""
 
     def __init__(self, cands, n_obj, total_samples, device=None, buffers=None, group=None, float_type=None,
-                 ts_features=1024, ts_seed=0, fit_method="powell"):
+                 ts_features=1024, ts_seed=0, fit_method="powell", mes_samples=DEFAULT_MES_SAMPLES):
         from .distributed import shard_range
         self.dev = require_device(device)
         self.float_type = resolve_float_type(float_type)
@@ -152,6 +154,9 @@ class DeviceBackend:
         # ranks score the same posterior draws without a collective for them.
         self.ts_features = int(ts_features)
         self._ts_rng = np.random.default_rng(ts_seed)
+        # acquisition "mes": the posterior draws behind the sampled maxima come from the same
+        # generator, mes_samples of them anew every iteration
+        self.mes_samples = int(mes_samples)
 
     def fit(self, x_vector, y_vector, n, prior_mean, prior_variance, length_scales):
         """Returns (Powell's OptimizeResult, fitted device state, time after the Powell fit)."""
@@ -230,7 +235,9 @@ class DeviceBackend:
         top-q); "hvi" replaces the acquisition array with the exact hypervolume improvement of the
         UCB vectors over the Pareto front of `y_evaluated` above `reference_point`; "ehvi" with the
         expected hypervolume improvement of the posterior (mu_objectives, variance_objectives) over
-        that front (acquisition.ehvi_select_indices; not in the reference).
+        that front (acquisition.ehvi_select_indices; not in the reference); "mes" with the max-value
+        entropy search acquisition over the maxima of `mes_samples` posterior draws
+        (acquisition.mes_select_indices; not in the reference; up to 8 objectives, "top" only).
         batch_strategy "top" is the reference's batch (the batch_size best values of one
         acquisition array); "bucb" (not in the reference) takes every pick after the first from the
         UCB recomputed with the variance conditioned on the earlier picks
@@ -299,6 +306,26 @@ class DeviceBackend:
         predict_acquire(xd, yd, kinv, self.cands, prior_mean, prior_variance, length_scales, betas,
                         outputs=tuple(out), topq=0, offset=self.offset, count=self.count, out=out,
                         device=self.dev, mode=self.mode, float_type=self.float_type)
+        if acquisition == "mes":
+            # posterior draws over this shard (anew every iteration, the same on every rank), their
+            # maxima over ALL candidates (one all_reduce MAX with several ranks), the scan, the masked
+            # top-q, then the fused path's exchange; batches above BO_MAX_TOPQ: the scan only, then
+            # the rounds below
+            if self._excl_mask is None:
+                self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
+            draws = thompson_draws(self._ts_rng, len(prior_mean), self.cands.dim, xd.shape[0], self.mes_samples,
+                                   self.ts_features)
+            fits = batch_size <= _lib.MAX_TOPQ
+            rec = mes_select_indices(self.bufs.acquisition_values, self.bufs.mu_objectives,
+                                     self.bufs.variance_objectives, xd, yd, kinv, self.cands, prior_mean,
+                                     prior_variance, length_scales, draws, evaluated, batch_size,
+                                     offset=self.offset, return_record=True, mask=self._excl_mask,
+                                     float_type=self.float_type, group=self.group, select=fits)
+            if fits:
+                from .distributed import collectives_on, exchange_topq_rec
+                if not collectives_on(self.group):
+                    return _record_indices(rec, batch_size)
+                return np.asarray(exchange_topq_rec(rec, batch_size, self.group)[1], dtype=np.int64)
         if acquisition in ("hvi", "ehvi") and batch_size <= _lib.MAX_TOPQ:
             # the exact HVI and its top-q with exclusion in one device pass over this shard (the
             # EHVI: its scan, then the masked top-q), then the fused path's exchange
@@ -354,7 +381,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
              callbacks: Optional[List[Callable]] = None, *,
              acquisition: str = "sum_ucb", group=None, backend=None,
              float_type=None, batch_strategy: str = "top", ts_features: int = 1024,
-             ts_seed: int = 0, constraint_bounds=None, fit_method: str = "powell") -> Tuple[np.ndarray, np.ndarray, int]:
+             ts_seed: int = 0, constraint_bounds=None, fit_method: str = "powell",
+             mes_samples: int = DEFAULT_MES_SAMPLES) -> Tuple[np.ndarray, np.ndarray, int]:
     """bayesian_optimization.py:51-247 with the reference's argument list.
 
     `kernel_matrices` and the posterior arrays may be HIP tensors (in place) or numpy arrays;
@@ -386,6 +414,11 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     `fit_method` "lbfgs" fits the length scales by L-BFGS-B over log ls with the device's analytic
     MLL gradient (kernels.optimize_hyperparams_mll, method="lbfgs": prior_variance stays as given);
     "powell", the default, is the reference's fit.  It is the backend's when `backend` is given.
+    `acquisition` "mes" (not in the reference; 1 to 8 objectives, batch_strategy "top" only, any
+    number of ranks) is the max-value entropy search acquisition (acquisition.max_value_entropy)
+    over the maxima of `mes_samples` posterior draws (1 .. BO_MAX_TOPQ, default 8; drawn anew every
+    iteration from default_rng(`ts_seed`) with `ts_features` features, the same on every rank; the
+    backend's when `backend` is given).
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -398,6 +431,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         _check_constraints(n_obj - len(constraint_bounds), len(constraint_bounds), constraint_bounds, acquisition,
                            batch_strategy)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, getattr(backend, "group", group))
+    if acquisition == "mes":
+        _check_mes_samples(getattr(backend, "mes_samples", mes_samples))
     if backend is None:
         dev = require_device()
         cands = input_space if isinstance(input_space, CandidateSet) else CandidateSet.explicit(input_space, dev)
@@ -419,7 +454,8 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
         bufs.ucb = dev_buf(ucb, (n_obj, cnt))
         bufs.acquisition_values = dev_buf(acquisition_values, (cnt,))
         backend = DeviceBackend(cands, n_obj, total_samples, dev, bufs, group, float_type=float_type,
-                                ts_features=ts_features, ts_seed=ts_seed, fit_method=fit_method)
+                                ts_features=ts_features, ts_seed=ts_seed, fit_method=fit_method,
+                                mes_samples=mes_samples)
     cands, rank, world = backend.cands, backend.rank, backend.world
     gather = bool(callbacks)
     bgroup = getattr(backend, "group", group)
@@ -500,6 +536,13 @@ def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
     if batch_strategy not in ALL_BATCH_STRATEGIES:
         raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top', 'bucb' or 'ts', "
                          "or 'kb' with acquisition='ehvi')")
+    if acquisition == "mes" and batch_strategy != "top":
+        why = {"bucb": "'bucb' conditions the UCB acquisition ('sum_ucb')",
+               "ts": "'ts' scores one posterior draw per pick, and 'mes' already averages over its draws' maxima: "
+                     "it has no per-draw form",
+               "kb": "'kb' extends the EHVI's front by believed observations"}[batch_strategy]
+        raise ValueError(f"acquisition='mes' supports batch_strategy='top' only (got {batch_strategy!r}): {why}; "
+                         "a batch for the max-value entropy would need the variance conditioned on the earlier picks")
     if batch_strategy == "kb":
         if acquisition != "ehvi":
             raise ValueError("batch_strategy='kb' (Kriging believer) extends the front by believed observations: "
@@ -560,14 +603,22 @@ def _check_constraints(n_obj, n_con, constraint_bounds, acquisition, batch_strat
     check_constraint_bounds(constraint_bounds, n_con)
 
 
+def _check_mes_samples(mes_samples):
+    if not 1 <= int(mes_samples) <= _lib.MAX_TOPQ:
+        raise ValueError(f"mes_samples must be in [1, {_lib.MAX_TOPQ}] (got {mes_samples}): the posterior draws "
+                         "of one bo_sample_paths call")
+
+
 def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", batch_strategy="top", group=None,
-                  n_constraints=0, constraint_bounds=None, fit_method="powell"):
+                  n_constraints=0, constraint_bounds=None, fit_method="powell", mes_samples=DEFAULT_MES_SAMPLES):
     """Fail in the constructor -- before any objective evaluation -- on shapes the device path
     cannot run (the reference would hit them only mid-loop, if at all).  n_obj counts the
     objectives; the n_constraints outcome constraints are further outputs."""
     check_fit_method(fit_method)
     _check_constraints(n_obj, n_constraints, constraint_bounds, acquisition, batch_strategy)
     _check_batch_strategy(batch_strategy, acquisition, batch_size, group)
+    if acquisition == "mes":
+        _check_mes_samples(mes_samples)
     if not 1 <= n_obj <= _lib.MAX_OBJ:
         raise ValueError(f"n_objectives must be in [1, {_lib.MAX_OBJ}] (got {n_obj})")
     if acquisition == "hvi" and n_obj > 4:
@@ -598,7 +649,10 @@ class BayesianOptimization:
     a Sobol set, or a CandidateSet such as CandidateSet.sobol_set(...), instead of the integer
     grid), ``device``, ``acquisition`` ("sum_ucb", the reference's default; "hvi": exact
     hypervolume improvement of the UCB vectors over the evaluated Pareto front; or "ehvi": the
-    expected hypervolume improvement of the posterior over that front, objectives independent),
+    expected hypervolume improvement of the posterior over that front, objectives independent; or
+    "mes": max-value entropy search, acquisition.max_value_entropy, for 1 to 8 objectives and
+    batch_strategy "top", over the maxima of ``mes_samples`` posterior draws, default 8, drawn anew
+    every iteration from the ``ts_seed`` generator with ``ts_features`` features),
     ``reference_point`` (the HVI reference point; the reference fixes it at zeros and never uses
     it, bayesian_optimization.py:425), ``group`` (the torch.distributed process group of a
     multi-GPU run; default: the world when initialised), ``float_type`` (np.float64, the default
@@ -678,8 +732,10 @@ class BayesianOptimization:
         if not 1 <= self.ts_features <= _lib.TS_MAX_FEATURES:
             raise ValueError(f"ts_features must be in [1, {_lib.TS_MAX_FEATURES}] (got {self.ts_features})")
         self.fit_method = kwargs.get("fit_method", "powell")
+        self.mes_samples = kwargs.get("mes_samples", DEFAULT_MES_SAMPLES)
         _check_limits(n_objectives, self.dim, self.total_samples, self.batch_size, self.acquisition,
-                      self.batch_strategy, self.group, self.n_constraints, self.constraint_bounds, self.fit_method)
+                      self.batch_strategy, self.group, self.n_constraints, self.constraint_bounds, self.fit_method,
+                      self.mes_samples)
         self.reference_point = np.array(kwargs.get("reference_point", [0.0] * n_objectives), dtype=ft)
         if self.constraint_bounds is not None:
             self.constraint_bounds = check_constraint_bounds(self.constraint_bounds, self.n_constraints)
@@ -694,7 +750,8 @@ class BayesianOptimization:
         self.y_vector = np.zeros((self.total_samples, n_out), dtype=ft)
         self._backend = DeviceBackend(self.candidates, n_out, self.total_samples, self.device,
                                       group=self.group, float_type=ft, ts_features=self.ts_features,
-                                      ts_seed=self.ts_seed, fit_method=self.fit_method)
+                                      ts_seed=self.ts_seed, fit_method=self.fit_method,
+                                      mes_samples=self.mes_samples)
         self._buffers = self._backend.bufs
         self.k_star = None   # never materialised (the reference allocates n_obj x T x M here)
         rank, world = _world(self.group)
@@ -751,7 +808,8 @@ class BayesianOptimization:
             bounds=self.bounds, callbacks=self.callbacks if self.callbacks else None,
             acquisition=self.acquisition, group=self.group, backend=self._backend,
             float_type=self.float_type, batch_strategy=self.batch_strategy, ts_features=self.ts_features,
-            ts_seed=self.ts_seed, constraint_bounds=self.constraint_bounds, fit_method=self.fit_method)
+            ts_seed=self.ts_seed, constraint_bounds=self.constraint_bounds, fit_method=self.fit_method,
+            mes_samples=self.mes_samples)
 
     def pareto_analysis(self) -> np.ndarray:
         """bayesian_optimization.py:465-488.  With outcome constraints: the front of the feasible

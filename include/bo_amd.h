@@ -500,6 +500,60 @@ int bo_constrained_ehvi(double* acq, double* pof_out, const double* mu, const do
                         int32_t form, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Max-value entropy search for multi-objective problems (MESMO: Belakaria, Deshwal & Doppa 2019,
+ * after Wang & Jegelka 2017; opt-in acquisition "mes").  NOT in the reference: parity is unpinned
+ * by it (tests/mes_ref.py is the independent statement).  Its cost is linear in the number of
+ * objectives (1 <= n_obj <= BO_MAX_OBJ), and it needs no reference point and no front.  With
+ * candidate c's posterior mu_k(c), var_k(c) (the predict's mu_objectives / variance_objectives),
+ * sigma_k = sqrt(|var_k|) (the UCB's and the EHVI's convention) and S posterior draws f_sk
+ * (bo_sample_paths' `paths` mapped back to objective units):
+ *   y*_sk  = max over ALL candidates c of f_sk(c)          (evaluated points included)
+ *   gamma  = (y*_sk - mu_k(c)) / sigma_k(c)                (as fl(fl(y* - mu) fl(1 / sigma)))
+ *   g(x)   = x phi(x) / (2 Phi(x)) - ln Phi(x)             (>= 0, decreasing, g(0) = ln 2)
+ *   acq(c) = (1/S) sum_s sum_k g(gamma_sk(c))
+ * g(x) is the entropy of N(0, 1) minus the entropy of N(0, 1) truncated above at x: acq is the
+ * expected reduction of the entropy of Y(c) given that no objective exceeds its sampled maximum.
+ * g is evaluated in three branches (both tails of the textbook form are lost in f64):
+ *   x >= 0:         q = erfc(x / sqrt 2) / 2;  g = x phi(x) / (2 (1 - q)) - log1p(-q)
+ *   -2^27 < x < 0:  t = -x / sqrt 2, E = erfcx(t);  g = t^2 - t / (sqrt(pi) E) - ln(E / 2)
+ *   x <= -2^27:     g = ln(-x) + (ln(2 pi) - 1) / 2    (-inf included)
+ * LIMITS: sigma = 0 gives g = 0 if y* >= mu, else +inf; y* = +inf gives 0 and y* = -inf gives
+ * +inf; NaN in any mu_k, var_k or y*_sk gives acq = NaN (selected first, as everywhere else).
+ * The summation order is fixed -- s outer, k inner, one f64 accumulator, then one multiplication
+ * by fl(1 / S) -- so the result is deterministic and a candidate's bits do not depend on its shard.
+ * ROUNDING RULE: with u = 2^-53 and the reference g_ref, acq_ref computed in extended precision
+ * from the same f64 mu, var and y* (the device's own y* taken as data),
+ *   |acq - acq_ref| <= u / S sum_sk [32 (1 + gamma_sk^2 / 2) + S n_obj] g_ref(gamma_sk) + 2^-1022:
+ * 1 + gamma^2 / 2 is the conditioning of exp(-gamma^2 / 2) and of the middle branch's
+ * cancellation (t^2 - t / (sqrt(pi) E) -> -1/2); of the 32, the f64 evaluation of the three
+ * branches measures 10.8 at worst (near x = -0.003), the three roundings of gamma add at most 6,
+ * and the rest is left to the device's erfcx / exp / log.
+ *
+ * bo_path_maxima: ystar[r] = fl(shift_k + scale_k max_j paths[r][j]) -- one rounding, an fma --
+ * for each of the n_samples * n_obj rows r = s * n_obj + k of `paths` (device, row stride ld,
+ * columns [0, n_cand)); `ystar` is device [n_samples][n_obj]; shift / scale are HOST [n_obj],
+ * passed to the kernel by value (the loop: prior_mean and sqrt(prior_variance)).  NaN entries are
+ * ignored; an all-NaN or empty row gives NaN; a zero maximum of either sign counts as +0.  The
+ * max is exact, so the result does not depend on the reduction order, and, the map being monotone
+ * for scale > 0, the max over per-shard results is bit-equal to the unsharded result (several
+ * ranks combine with one all-reduce MAX).  One pass over `paths`, fixed-order partial maxima in
+ * the workspace, one finishing workgroup; no atomics.  The workspace size query returns 0 for
+ * n_cand < 0 or n_rows outside [1, BO_MAX_TOPQ * BO_MAX_OBJ].
+ * bo_max_value_entropy: the scan; acq is device [n], mu / var device [n_obj][ld], ystar device
+ * [n_samples][n_obj], 1 <= n_samples <= BO_MAX_TOPQ, 1 <= n_obj <= BO_MAX_OBJ.  One thread per
+ * candidate.
+ * Both check every argument before the device is touched: BO_ERR_ARG for a NULL pointer (`paths` may be NULL when n_cand = 0: nothing is read), n_obj or
+ * n_samples out of range, ld < n (ld < n_cand), a negative n, scale <= 0 or a non-finite scale or
+ * shift; BO_ERR_WORKSPACE for a missing or short workspace.  Both are asynchronous on `stream`,
+ * capturable in a HIP graph, deterministic, and synchronise with nothing. */
+size_t bo_path_maxima_workspace_size(int64_t n_cand, int64_t n_rows);
+int bo_path_maxima(double* ystar, const double* paths, int64_t ld, int64_t n_cand,
+                   int32_t n_samples, int32_t n_obj, const double* shift, const double* scale,
+                   void* workspace, size_t workspace_bytes, void* stream);
+int bo_max_value_entropy(double* acq, const double* mu, const double* var, int64_t ld, int64_t n,
+                         int32_t n_obj, const double* ystar, int32_t n_samples, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Kriging-believer batches for the EHVI (Ginsbourger, Le Riche & Carraro 2010; opt-in
  * batch_strategy "kb").  NOT in the reference.  The q best values of one EHVI array are q
  * neighbours of one maximum; here the picks are taken one after the other, and after each one the
