@@ -56,7 +56,7 @@ class PredictDesc(C.Structure):
     ]
 
 
-# bo_bucb_desc and bo_kb_desc open with the same fields: the fitted state, the picks, the candidates
+# bo_bucb_desc, bo_kb_desc and bo_gibbon_desc open with the same fields: the fitted state, the picks, the candidates
 _UPDATE_FIELDS = [
     ("n_obj", C.c_int32), ("dim", C.c_int32), ("n_train", C.c_int64),
     ("x_train", c_vp), ("kinv", c_vp), ("ld_k", C.c_int64),
@@ -89,6 +89,16 @@ class KbDesc(C.Structure):
         ("host_ws", c_vp), ("host_ws_bytes", C.c_size_t),
         ("top_val", c_vp), ("top_idx", c_vp), ("believed", c_vp), ("var_out", c_vp),
         ("acq_first", c_vp), ("acq_last", c_vp), ("n_boxes_max", C.POINTER(C.c_int64)),
+    ]
+
+
+class GibbonDesc(C.Structure):
+    """Mirror of bo_gibbon_desc (include/bo_amd.h)."""
+
+    _fields_ = _UPDATE_FIELDS + [
+        ("jitter", C.c_double), ("min_variance", C.c_double),
+        ("base", c_vp), ("var", c_vp), ("ld", C.c_int64), ("mask", c_vp),
+        ("top_val", c_vp), ("top_idx", c_vp), ("var_out", c_vp), ("acq_last", c_vp),
     ]
 
 
@@ -177,6 +187,8 @@ _SIGS = {
     "bo_select_batch_kb_workspace_size": (C.c_size_t, [C.POINTER(KbDesc)]),
     "bo_select_batch_kb_host_workspace_size": (C.c_size_t, [C.POINTER(KbDesc)]),
     "bo_select_batch_kb": (C.c_int, [C.POINTER(KbDesc), c_vp, C.c_size_t, c_vp]),
+    "bo_select_batch_gibbon_workspace_size": (C.c_size_t, [C.POINTER(GibbonDesc)]),
+    "bo_select_batch_gibbon": (C.c_int, [C.POINTER(GibbonDesc), c_vp, C.c_size_t, c_vp]),
     "bo_sample_paths_workspace_size":(C.c_size_t, [C.POINTER(TsDesc)]),
     "bo_sample_paths": (C.c_int, [C.POINTER(TsDesc), c_vp, C.c_size_t, c_vp]),
     "bo_pareto_mask": (C.c_int, [c_vp, C.c_int64, C.c_int32, c_vp, c_vp]),

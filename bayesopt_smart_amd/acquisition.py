@@ -1000,9 +1000,91 @@ def update_max_value_entropy(acquisition_values, mu_objectives, variance_objecti
     max_value_entropy(mu_objectives, variance_objectives, ystar, out=acquisition_values)
 
 
+MES_BATCH_STRATEGIES = ("top", "gibbon")               # the batches of acquisition="mes"
+
+
+def select_batch_gibbon(base, variance_objectives, x_train, kinv, cands, prior_variance, length_scales,
+                        evaluated_points, batch_size, offset=0, count=None, mask=None, float_type=None,
+                        jitter=None, min_variance=None, return_variance=False, return_details=False):
+    """A batch for an information criterion whose later picks account for the earlier ones (GIBBON's
+    greedy batch bound, Moss, Leslie, Gonzalez & Rayson 2021; bo_select_batch_gibbon,
+    include/bo_amd.h states the definition).  NOT in the reference.  The first pick is the masked
+    top-1 of `base`; pick t > 1 is the best candidate of
+    base + 0.5 sum_o log(var_o^(t-1) / var_o^0), where var^(t-1) is the variance conditioned on picks
+    1..t-1 as hallucinated observations (select_batch_bucb's update) and var^0 the given one: the
+    greedy increment of half the log-determinant of the batch's predictive correlation matrix.
+
+    base: the single-point acquisition over the shard [offset, offset + count) of `cands` (device
+    [count]; in the loop the max-value entropy array -- any array will do); variance_objectives:
+    the predict's output over that shard (device [n_obj, >= count]); neither is modified.  x_train
+    [N, d] and kinv [n_obj, N, N]: the fitted state the predict used.  `mask`: this shard's
+    ExclusionMask, updated here with evaluated_points; without one a mask is built for the call.
+    jitter / min_variance default to KERNEL_JITTER / MIN_VARIANCE of `float_type`'s branch.  One
+    device call, no host synchronisation between the picks.  Returns the global indices of the
+    picks (fewer than batch_size when the shard runs out of candidates) -- with `return_variance`,
+    also the conditioned variance (device [n_obj, count]); with `return_details`, a dict (top_idx,
+    top_val, var, acq_last: device tensors; acq_last is the array the last pick was taken from)."""
+    from .config import precision_constants
+    if not 1 <= batch_size <= _lib.MAX_TOPQ:
+        raise ValueError(f"select_batch_gibbon handles 1 <= batch_size <= {_lib.MAX_TOPQ}")
+    dev = _dev_of(base, variance_objectives)
+    b = _Arg(base, dev)
+    var = _Arg(variance_objectives, dev)
+    if var.t.dim() != 2 or not 1 <= var.t.shape[0] <= _lib.MAX_OBJ:
+        raise ValueError(f"variance must be [n_obj, >= count] with 1 <= n_obj <= {_lib.MAX_OBJ}")
+    n_obj = var.t.shape[0]
+    count = int(cands.n - offset if count is None else count)
+    if var.t.shape[1] < count:
+        raise ValueError(f"variance must be [n_obj, >= count] (count = {count})")
+    if b.t.dim() != 1 or b.t.numel() != count:
+        raise ValueError(f"base must hold one value for each of the {count} candidates")
+    x = torch.as_tensor(x_train, dtype=F64, device=dev).contiguous()
+    kinv = torch.as_tensor(kinv, dtype=F64, device=dev).contiguous()
+    n = x.shape[0]
+    if not _fitted_ok(x, kinv, cands.dim, n_obj):
+        raise ValueError("x_train must be [N, d] and kinv [n_obj, >=N, >=N]")
+    kj, _, mv = precision_constants(float_type)
+    mask = _shard_mask(mask, cands, offset, count, dev, evaluated_points, "select_batch_gibbon")
+    d = _lib.GibbonDesc()
+    d.n_obj, d.n_train, d.q = n_obj, n, batch_size
+    d.x_train, d.kinv, d.ld_k = x.data_ptr(), kinv.data_ptr(), kinv.shape[-1]
+    _set_cand_fields(d, cands, offset, count)
+    for o in range(n_obj):
+        d.prior_var[o] = float(prior_variance[o])
+        d.length_scale[o] = float(length_scales[o])
+    d.jitter = float(kj if jitter is None else jitter)
+    d.min_variance = float(mv if min_variance is None else min_variance)
+    d.base, d.var = b.ptr, var.ptr
+    d.ld = var.t.shape[1]                              # _Arg: contiguous
+    d.mask = mask.ptr
+    tv = torch.empty(batch_size, dtype=F64, device=dev)
+    ti = torch.empty(batch_size, dtype=torch.int64, device=dev)
+    d.top_val, d.top_idx = tv.data_ptr(), ti.data_ptr()
+    var_out = acq_last = None
+    if return_variance or return_details:
+        var_out = torch.empty((n_obj, d.ld), dtype=F64, device=dev)
+        d.var_out = var_out.data_ptr()
+    if return_details:
+        acq_last = torch.empty(count, dtype=F64, device=dev)
+        d.acq_last = acq_last.data_ptr()
+    lib = _lib.load()
+    nbytes = lib.bo_select_batch_gibbon_workspace_size(d)
+    if nbytes == 0:
+        raise _lib.BoNativeError(_lib.ERR_ARG, "bo_select_batch_gibbon_workspace_size")
+    ws = Workspace.get(nbytes, dev)
+    _lib.check(lib.bo_select_batch_gibbon(d, ws.data_ptr(), ws.numel(), stream_handle(dev)),
+               "bo_select_batch_gibbon")
+    if return_details:
+        return {"top_idx": ti, "top_val": tv, "var": var_out[:, :count], "acq_last": acq_last}
+    idx = ti.cpu().numpy()
+    idx = idx[idx >= 0].astype(np.int64)
+    return (idx, var_out[:, :count]) if return_variance else idx
+
+
 def mes_select_indices(acquisition_values, mu_objectives, variance_objectives, x_train, y_train, kinv, cands,
                        prior_mean, prior_variance, length_scales, draws, evaluated_points, batch_size, offset=0,
-                       return_record=False, mask=None, float_type=None, jitter=None, group=None, select=True):
+                       return_record=False, mask=None, float_type=None, jitter=None, group=None, select=True,
+                       batch_strategy="top"):
     """The max-value entropy search acquisition and its batch selection over one shard, shaped like
     ehvi_select_indices: the posterior draws over the shard (sample_paths with `draws`, as
     thompson_draws returns them -- every rank the same), their maxima (path_maxima: over ALL
@@ -1013,7 +1095,17 @@ def mes_select_indices(acquisition_values, mu_objectives, variance_objectives, x
     evaluated_points; without one a mask is built for the call).  batch_size <= BO_MAX_TOPQ.
     Returns the global indices of the shard's best batch_size candidates not equal to an evaluated
     point (select_next_batch's order, NaN first) -- or, `return_record`, the device record block
-    [2 batch_size] for the multi-rank exchange.  `select` False: the scan only (returns None)."""
+    [2 batch_size] for the multi-rank exchange.  `select` False: the scan only (returns None).
+    `batch_strategy` "gibbon" (one rank, so no record block): the scan as above, then
+    select_batch_gibbon on it -- every pick after the first is penalised by half the log-ratio of
+    the variance conditioned on the earlier picks to the unconditioned one (jitter as the draws',
+    the floor of `float_type`'s branch); returns the global indices of the picks."""
+    if batch_strategy not in MES_BATCH_STRATEGIES:
+        raise ValueError(f"unknown batch_strategy {batch_strategy!r} for the max-value entropy "
+                         f"(expected one of {MES_BATCH_STRATEGIES})")
+    if batch_strategy == "gibbon" and (return_record or not select):
+        raise ValueError("batch_strategy='gibbon' runs on one rank and returns its picks: it has no record block "
+                         "and no scan-only form")
     if select and batch_size > _lib.MAX_TOPQ:
         raise ValueError(f"mes_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
     dev = _dev_of(acquisition_values, mu_objectives)
@@ -1027,6 +1119,12 @@ def mes_select_indices(acquisition_values, mu_objectives, variance_objectives, x
         acq.finish()
         return None
     mask = _shard_mask(mask, cands, offset, n, dev, evaluated_points, "mes_select_indices")
+    if batch_strategy == "gibbon":
+        idx = select_batch_gibbon(acq.t, variance_objectives, x_train, kinv, cands, prior_variance, length_scales,
+                                  evaluated_points, batch_size, offset=offset, count=n, mask=mask,
+                                  float_type=float_type, jitter=jitter)
+        acq.finish()
+        return idx
     rec = torch.empty(2 * batch_size, dtype=F64, device=dev)
     lib = _lib.load()
     ws = Workspace.get(lib.bo_select_topq_workspace_size(n, batch_size), dev)

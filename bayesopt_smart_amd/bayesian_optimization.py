@@ -29,7 +29,8 @@ import numpy as np
 import torch
 
 from . import kernels as K
-from .acquisition import (ALL_BATCH_STRATEGIES, ExclusionMask, _record_indices, check_constraint_bounds,
+from .acquisition import (ALL_BATCH_STRATEGIES, MES_BATCH_STRATEGIES, ExclusionMask, _record_indices,
+                          check_constraint_bounds,
                           ehvi_select_indices, feasible_rows, hvi_select_indices, mes_select_indices,
                           select_batch_bucb,
                           select_batch_kb, select_batch_ts,
@@ -237,7 +238,7 @@ class DeviceBackend:
         expected hypervolume improvement of the posterior (mu_objectives, variance_objectives) over
         that front (acquisition.ehvi_select_indices; not in the reference); "mes" with the max-value
         entropy search acquisition over the maxima of `mes_samples` posterior draws
-        (acquisition.mes_select_indices; not in the reference; up to 8 objectives, "top" only).
+        (acquisition.mes_select_indices; not in the reference; up to 8 objectives, "top" or "gibbon").
         batch_strategy "top" is the reference's batch (the batch_size best values of one
         acquisition array); "bucb" (not in the reference) takes every pick after the first from the
         UCB recomputed with the variance conditioned on the earlier picks
@@ -248,7 +249,11 @@ class DeviceBackend:
         collective is needed for them and the exchange of the top-q records merges the shards;
         "kb" (not in the reference; "ehvi" only, one rank) takes every pick after the first from
         the EHVI of the variance conditioned on the earlier picks over the front extended by the
-        posterior means at those picks (Kriging believer, acquisition.select_batch_kb).
+        posterior means at those picks (Kriging believer, acquisition.select_batch_kb);
+        "gibbon" (not in the reference; "mes" only, one rank) takes every pick after the first from
+        the max-value entropy array plus half the log-ratio of the variance conditioned on the
+        earlier picks to the unconditioned one, summed over the objectives (GIBBON's greedy batch
+        bound, acquisition.select_batch_gibbon).
         `constraint_bounds` (not in the reference; "ehvi" and "top" only): the last
         len(constraint_bounds) outputs are outcome constraints, y_evaluated carries them after the
         objectives, and the acquisition is the EHVI over the front of the feasible evaluated
@@ -315,6 +320,14 @@ class DeviceBackend:
                 self._excl_mask = ExclusionMask(self.cands, self.offset, self.count, self.dev)
             draws = thompson_draws(self._ts_rng, len(prior_mean), self.cands.dim, xd.shape[0], self.mes_samples,
                                    self.ts_features)
+            if batch_strategy == "gibbon":
+                # one rank, batch_size <= BO_MAX_TOPQ (_check_batch_strategy): the scan, then the
+                # picks penalised by the variance conditioned on the earlier ones
+                return mes_select_indices(self.bufs.acquisition_values, self.bufs.mu_objectives,
+                                          self.bufs.variance_objectives, xd, yd, kinv, self.cands, prior_mean,
+                                          prior_variance, length_scales, draws, evaluated, batch_size,
+                                          offset=self.offset, mask=self._excl_mask, float_type=self.float_type,
+                                          group=self.group, batch_strategy="gibbon")
             fits = batch_size <= _lib.MAX_TOPQ
             rec = mes_select_indices(self.bufs.acquisition_values, self.bufs.mu_objectives,
                                      self.bufs.variance_objectives, xd, yd, kinv, self.cands, prior_mean,
@@ -414,11 +427,16 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     `fit_method` "lbfgs" fits the length scales by L-BFGS-B over log ls with the device's analytic
     MLL gradient (kernels.optimize_hyperparams_mll, method="lbfgs": prior_variance stays as given);
     "powell", the default, is the reference's fit.  It is the backend's when `backend` is given.
-    `acquisition` "mes" (not in the reference; 1 to 8 objectives, batch_strategy "top" only, any
-    number of ranks) is the max-value entropy search acquisition (acquisition.max_value_entropy)
-    over the maxima of `mes_samples` posterior draws (1 .. BO_MAX_TOPQ, default 8; drawn anew every
-    iteration from default_rng(`ts_seed`) with `ts_features` features, the same on every rank; the
-    backend's when `backend` is given).
+    `acquisition` "mes" (not in the reference; 1 to 8 objectives, batch_strategy "top" with any
+    number of ranks, or "gibbon" on one rank) is the max-value entropy search acquisition
+    (acquisition.max_value_entropy) over the maxima of `mes_samples` posterior draws
+    (1 .. BO_MAX_TOPQ, default 8; drawn anew every iteration from default_rng(`ts_seed`) with
+    `ts_features` features, the same on every rank; the backend's when `backend` is given).
+    `batch_strategy` "gibbon" (acquisition "mes" only, one rank, batch_size <= BO_MAX_TOPQ) computes
+    that array once and takes every pick after the first from it plus GIBBON's batch correction,
+    half the log-ratio of the variance conditioned on the earlier picks to the unconditioned one
+    summed over the objectives (acquisition.select_batch_gibbon): the batch spreads instead of
+    crowding one maximum.
 
     Callbacks with several ranks: the state arrays are the shards gathered, a collective; whether
     to gather is decided once, collectively (any rank with callbacks), so that a callback
@@ -532,17 +550,30 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
 
 
 def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
-    """What batch_strategy="bucb" / "ts" / "kb" do not cover raises here, with the reason."""
-    if batch_strategy not in ALL_BATCH_STRATEGIES:
+    """What batch_strategy="bucb" / "ts" / "kb" / "gibbon" do not cover raises here, with the reason."""
+    if batch_strategy not in ALL_BATCH_STRATEGIES + MES_BATCH_STRATEGIES:
         raise ValueError(f"unknown batch_strategy {batch_strategy!r} (expected 'top', 'bucb' or 'ts', "
-                         "or 'kb' with acquisition='ehvi')")
+                         "or 'kb' with acquisition='ehvi'), or 'gibbon' with acquisition='mes'")
+    if batch_strategy == "gibbon":
+        if acquisition != "mes":
+            raise ValueError("batch_strategy='gibbon' adds half the log-ratio of the conditioned to the "
+                             "unconditioned variance: the penalty is the batch correction of an information "
+                             f"criterion, defined for acquisition='mes' only (got acquisition={acquisition!r})")
+        if batch_size > _lib.MAX_TOPQ:
+            raise ValueError(f"batch_strategy='gibbon' supports batch_size <= {_lib.MAX_TOPQ} (got {batch_size})")
+        from .distributed import collectives_on
+        if collectives_on(group):
+            raise ValueError("batch_strategy='gibbon' runs on one rank: with several, every pick would need an "
+                             "all-gather of the per-rank best candidates")
+        return
     if acquisition == "mes" and batch_strategy != "top":
         why = {"bucb": "'bucb' conditions the UCB acquisition ('sum_ucb')",
                "ts": "'ts' scores one posterior draw per pick, and 'mes' already averages over its draws' maxima: "
                      "it has no per-draw form",
                "kb": "'kb' extends the EHVI's front by believed observations"}[batch_strategy]
         raise ValueError(f"acquisition='mes' supports batch_strategy='top' only (got {batch_strategy!r}): {why}; "
-                         "a batch for the max-value entropy would need the variance conditioned on the earlier picks")
+                         "a batch for the max-value entropy would need the variance conditioned on the earlier picks "
+                         "(batch_strategy='gibbon' is that batch)")
     if batch_strategy == "kb":
         if acquisition != "ehvi":
             raise ValueError("batch_strategy='kb' (Kriging believer) extends the front by believed observations: "
@@ -651,7 +682,7 @@ class BayesianOptimization:
     hypervolume improvement of the UCB vectors over the evaluated Pareto front; or "ehvi": the
     expected hypervolume improvement of the posterior over that front, objectives independent; or
     "mes": max-value entropy search, acquisition.max_value_entropy, for 1 to 8 objectives and
-    batch_strategy "top", over the maxima of ``mes_samples`` posterior draws, default 8, drawn anew
+    batch_strategy "top" or "gibbon", over the maxima of ``mes_samples`` posterior draws, default 8, drawn anew
     every iteration from the ``ts_seed`` generator with ``ts_features`` features),
     ``reference_point`` (the HVI reference point; the reference fixes it at zeros and never uses
     it, bayesian_optimization.py:425), ``group`` (the torch.distributed process group of a
@@ -668,7 +699,10 @@ class BayesianOptimization:
     ranks need no collective for the draws; or "kb", with acquisition "ehvi" only: a Kriging
     believer, every pick after the first maximises the EHVI of the variance conditioned on the
     earlier picks over the front extended by the posterior means there,
-    acquisition.select_batch_kb), and ``n_constraints`` with ``constraint_bounds`` (outcome
+    acquisition.select_batch_kb; or "gibbon", with acquisition "mes" only: every pick after the first
+    maximises the max-value entropy array plus half the log-ratio of the variance conditioned on
+    the earlier picks to the unconditioned one, GIBBON's greedy batch bound,
+    acquisition.select_batch_gibbon), and ``n_constraints`` with ``constraint_bounds`` (outcome
     constraints, acquisition "ehvi" and batch_strategy "top" only: ``function`` returns
     n_objectives + n_constraints values, the objectives first; constraint j is feasible inside
     constraint_bounds[j] = (lo, hi), either infinite on its own side; y_vector has

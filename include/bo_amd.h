@@ -642,6 +642,70 @@ int bo_select_batch_kb(const bo_kb_desc* desc, void* workspace, size_t workspace
                        void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * GIBBON batches for an information criterion (Moss, Leslie, Gonzalez & Rayson 2021; opt-in
+ * batch_strategy "gibbon" of acquisition "mes").  NOT in the reference.  The q best values of one
+ * max-value entropy array are q neighbours of one maximum.  GIBBON's batch criterion is the sum of
+ * the single-point information terms plus, per objective, half the log-determinant of the batch's
+ * predictive correlation matrix R_o; taken greedily, the increment of log det R_o for a candidate j
+ * after picks p_1..p_(t-1) is log(var_o^(t-1)[j] / var_o^0[j]) (Schur complement).  So the
+ * single-point array is computed once, with the unconditioned variance, and a later pick adds a
+ * penalty to it.  Inputs: `base` (device [n_cand]: the single-point acquisition -- in the loop
+ * bo_max_value_entropy's array; the call does not care what it is), `var` = var^0 (the predict's
+ * variance_objectives, [n_obj][ld], floored), the fitted state (x_train, kinv), the candidates as
+ * in bo_bucb_desc, jitter and min_variance.  For t = 1..q:
+ *   acq_1[j] = base[j], bit for bit (the first pass adds nothing: a NaN in `var` enters from
+ *              acq_2 on)
+ *   acq_t[j] = fl(base[j] + 0.5 P),  P = sum_o log(fl(var_o^(t-1)[j] / var_o^0[j])), summed in
+ *              f64 with o ascending, for t > 1; an objective with var_o^0[j] == 0 contributes 0;
+ *              NaN in base, var^0 or var^(t-1) gives NaN (selected first, as everywhere else)
+ *   p_t      = the best candidate of acq_t in the order of bo_select_topq (NaN first, then
+ *              descending value, then ascending global index) among those neither masked nor
+ *              already picked
+ *   var^t    = the recursion c_t, d_t, v_t of bo_bucb_desc for a pick at p_t, floored at
+ *              min_variance; unchanged for an objective whose d_t is not finite
+ * When no candidate is left, top_idx[t] = -1 and top_val[t] = -inf, for this pick and all later
+ * ones.  q = 1 is the masked top-1 of `base`.  q <= BO_MAX_TOPQ, n_obj <= BO_MAX_OBJ; every
+ * candidate kind, shards by cand_offset / n_cand.  base / var / mask are not modified.
+ * Asynchronous on its stream, no host synchronisation between the picks and -- unlike
+ * bo_select_batch_kb, there being no host step -- capturable in a HIP graph.  Deterministic:
+ * fixed-order reductions, no atomics; a workspace of any content gives the same bits.
+ * Every argument is checked before the device is touched: BO_ERR_ARG for a NULL base / var /
+ * x_train / kinv / top_val / top_idx (or `cand` of an explicit kind), an output that aliases an
+ * input, a misaligned workspace and what bo_select_batch_bucb refuses; BO_ERR_WORKSPACE for a
+ * missing or short workspace.  Fields shared with bo_bucb_desc have its meaning. */
+typedef struct bo_gibbon_desc {
+  int32_t n_obj;              /* objectives (<= BO_MAX_OBJ)                                   */
+  int32_t dim;                /* input dimensions (<= BO_MAX_DIM)                              */
+  int64_t n_train;            /* N >= 1                                                       */
+  const double* x_train;      /* device [n_train][dim]                                        */
+  const double* kinv;         /* device [n_obj][ld_k][ld_k]; leading N x N block = invert_k() */
+  int64_t ld_k;
+  int32_t cand_kind;          /* bo_cand_kind                                                 */
+  int32_t q;                  /* picks, 1 .. BO_MAX_TOPQ                                      */
+  const void* cand;           /* device [n_cand][dim] (kinds I64/F64); host bo_sobol_desc* (SOBOL) */
+  int64_t n_cand;             /* candidates of this call (a shard)                            */
+  int64_t cand_offset;        /* global index of this call's first candidate                  */
+  int64_t grid_lo[BO_MAX_DIM];     /* kind GRID                                              */
+  int64_t grid_shape[BO_MAX_DIM];  /* kind GRID (axis dim-1 fastest)                         */
+  double prior_var[BO_MAX_OBJ];
+  double length_scale[BO_MAX_OBJ];
+  double jitter;              /* KERNEL_JITTER added by invert_k: 1e-6 (1e-3 float32 branch)  */
+  double min_variance;        /* MIN_VARIANCE: 1e-10 (1e-6 float32 branch)                    */
+  const double* base;         /* device [n_cand]: the single-point acquisition                */
+  const double* var;          /* device [n_obj][ld]: var^0, variance_objectives (already floored) */
+  int64_t ld;                 /* row stride of var / var_out (>= n_cand)                      */
+  const uint32_t* mask;       /* device, bo_excl_mask_update's layout over this shard; NULL = none */
+  double* top_val;            /* device [q]: acq_t[p_t] (-inf when no candidate is left)      */
+  int64_t* top_idx;           /* device [q]: global index of pick t, -1 = no candidate left   */
+  double* var_out;            /* optional device [n_obj][ld]: var^q                           */
+  double* acq_last;           /* optional device [n_cand]: acq_q, the array pick q was taken from */
+} bo_gibbon_desc;
+/* bytes of device workspace bo_select_batch_gibbon needs for `desc` (0 on bad args) */
+size_t bo_select_batch_gibbon_workspace_size(const bo_gibbon_desc* desc);
+int bo_select_batch_gibbon(const bo_gibbon_desc* desc, void* workspace, size_t workspace_bytes,
+                           void* stream);
+
+/* ------------------------------------------------------------------------------------
  * GP fit on device.
  * ---------------------------------------------------------------------------------- */
 
