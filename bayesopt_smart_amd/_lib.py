@@ -209,6 +209,9 @@ _SIGS = {
     "bo_constrained_ehvi": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_dbl_p,
                                       c_dbl_p, c_vp, C.c_int64, c_vp, C.POINTER(C.c_int32), c_vp, C.c_int32,
                                       c_vp]),
+    "bo_logehvi_table_threads": (C.c_int, [C.c_int64]),
+    "bo_log_ehvi": (C.c_int, [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_dbl_p,
+                              c_dbl_p, c_vp, C.c_int64, c_vp, C.POINTER(C.c_int32), c_vp, C.c_int32, c_vp]),
     "bo_path_maxima_workspace_size": (C.c_size_t, [C.c_int64, C.c_int64]),
     "bo_path_maxima": (C.c_int, [c_vp, c_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, c_dbl_p, c_dbl_p,
                                  c_vp, C.c_size_t, c_vp]),

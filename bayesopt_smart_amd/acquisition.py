@@ -374,7 +374,8 @@ def ehvi_tables(boxes):
 class EhviTables:
     """What the EHVI scan reads besides mu / var, on the device: the boxes of the region `front`
     does not dominate above `reference_point` (direct form) and their edge tables (table form).
-    Built once per front; `threads` is the table form's workgroup size, 0 when no table fits."""
+    Built once per front; `threads` is the table form's workgroup size, 0 when no table fits
+    (`log_threads`: the same for the log-space scan, whose table holds 16 bytes per edge)."""
 
     def __init__(self, front, reference_point, device=None):
         self.dev = require_device(device)
@@ -385,6 +386,7 @@ class EhviTables:
         self.n_edges = (_C.c_int32 * self.n_obj)(*[len(e) for e in edges])
         self.sum_edges = int(sum(self.n_edges))
         self.threads = int(_lib.load().bo_ehvi_table_threads(self.sum_edges))
+        self.log_threads = int(_lib.load().bo_logehvi_table_threads(self.sum_edges))    # bo_log_ehvi's table
         self.boxes = torch.as_tensor(boxes, device=self.dev)
         self.edges = torch.as_tensor(np.concatenate(edges) if edges else np.zeros(0), device=self.dev)
         self.box_idx = torch.as_tensor(idx, device=self.dev)
@@ -489,9 +491,65 @@ def update_expected_hypervolume_improvement(acquisition_values, mu_objectives, v
                                      out=acquisition_values)
 
 
+def log_expected_hypervolume_improvement(mu, var, front, reference_point, constraint_bounds=None, out=None,
+                                         logpof_out=None, form="auto", tables=None):
+    """The natural logarithm of the EHVI -- with `constraint_bounds`, of the feasibility-weighted EHVI -- of
+    every candidate (bo_log_ehvi; include/bo_amd.h states the quantity, its limits and its rounding rule):
+    finite and correctly ordered where expected_hypervolume_improvement underflows to 0.0, -inf where the
+    exact value is 0, NaN where any row holds NaN.  mu / var: [n_obj + n_con, M], the objective rows first
+    (n_obj = len(reference_point), or tables.n_obj), numpy or HIP tensors; `front` with constraints: the
+    FEASIBLE evaluated points' objective vectors.  `logpof_out` ([M]) receives sum_j ln P_j.  `form` /
+    `tables` as expected_hypervolume_improvement's (same bits in both forms; the table holds 16 bytes per
+    edge and thread, EhviTables.log_threads).  Returns the values ([M], a device tensor, or numpy for numpy
+    `mu`); written into `out` when given (in place)."""
+    if form not in EHVI_FORMS:
+        raise ValueError(f"unknown form {form!r} (expected 'auto', 'direct' or 'table')")
+    bounds = check_constraint_bounds(constraint_bounds)
+    n_con = bounds.shape[0]
+    dev = _dev_of(out, mu)
+    m = _Arg(mu, dev)
+    v = _Arg(var, dev)
+    if m.t.dim() != 2 or v.t.shape != m.t.shape or m.t.stride(1) != 1 or v.t.stride() != m.t.stride():
+        raise ValueError("mu / var must both be [n_obj + n_con, M] with one row stride")
+    n_out, n = m.t.shape
+    tb = tables if tables is not None else EhviTables(front, reference_point, dev)
+    n_obj = tb.n_obj
+    if n_obj + n_con != n_out:
+        raise ValueError(f"the front has {n_obj} objectives and there are {n_con} constraints, mu has {n_out} rows")
+    acq = _Arg(out, dev, write=True) if out is not None else None
+    dst = acq.t if acq is not None else torch.empty(n, dtype=F64, device=dev)
+    if dst.numel() != n:
+        raise ValueError(f"out holds {dst.numel()} values for {n} candidates")
+    lpo = _Arg(logpof_out, dev, write=True) if logpof_out is not None else None
+    if lpo is not None and lpo.t.numel() != n:
+        raise ValueError(f"logpof_out holds {lpo.t.numel()} values for {n} candidates")
+    nb = tb.n_boxes
+    if n > 0:                                              # an empty tensor has no address to pass
+        _lib.check(_lib.load().bo_log_ehvi(
+            dst.data_ptr(), lpo.ptr if lpo is not None else None, m.ptr, v.ptr, max(m.t.stride(0), n), n, n_obj, n_con,
+            _host_vec(bounds[:, 0], n_con), _host_vec(bounds[:, 1], n_con),
+            tb.boxes.data_ptr() if nb else None, nb, tb.edges.data_ptr() if nb else None, tb.n_edges,
+            tb.box_idx.data_ptr() if nb else None, EHVI_FORMS[form], stream_handle(dev)), "bo_log_ehvi")
+    if lpo is not None:
+        lpo.finish()
+    if acq is not None:
+        acq.finish()
+        return out
+    return dst if isinstance(mu, torch.Tensor) else dst.cpu().numpy()
+
+
+def update_log_expected_hypervolume_improvement(acquisition_values, mu_objectives, variance_objectives, y_vector,
+                                                n_evaluations, reference_point, constraint_bounds=None):
+    """update_expected_hypervolume_improvement with the log-space scan (acquisition "logehvi"): the same
+    front (of the feasible rows with `constraint_bounds`), in place into `acquisition_values`."""
+    log_expected_hypervolume_improvement(
+        mu_objectives, variance_objectives, _front_of(y_vector, n_evaluations, reference_point, constraint_bounds),
+        reference_point, constraint_bounds=constraint_bounds, out=acquisition_values)
+
+
 def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, y_vector, n_evaluations,
                         reference_point, cands, evaluated_points, batch_size, offset=0, return_record=False,
-                        mask=None, constraint_bounds=None):
+                        mask=None, constraint_bounds=None, log=False):
     """The EHVI acquisition and its batch selection over one shard, in two launches: the EHVI scan
     into acquisition_values (device, [count]: the candidates [offset, offset + count) of `cands`,
     over the Pareto front of y_vector[:n_evaluations]), then bo_select_topq_masked over the shard's
@@ -501,14 +559,21 @@ def ehvi_select_indices(acquisition_values, mu_objectives, variance_objectives, 
     `return_record`, the device record block [2 batch_size] (values, bit-cast int64 indices) for
     the multi-rank exchange, as hvi_select_indices.  With `constraint_bounds` the scan is the
     constrained EHVI (constrained_expected_hypervolume_improvement) over the front of the feasible
-    rows of y_vector; infeasible evaluated points stay excluded like any evaluated point."""
+    rows of y_vector; infeasible evaluated points stay excluded like any evaluated point.  `log`: the
+    scan is log_expected_hypervolume_improvement (acquisition "logehvi"), the same selection over its
+    values; a free candidate whose value is -inf is an ordinary, lowest, value of that order."""
     if batch_size > _lib.MAX_TOPQ:
         raise ValueError(f"ehvi_select_indices handles batch_size <= {_lib.MAX_TOPQ}")
     dev = _dev_of(acquisition_values, mu_objectives)
     acq = _Arg(acquisition_values, dev, write=True)
     n = acq.t.numel()
     mask = _shard_mask(mask, cands, offset, n, dev, evaluated_points, "ehvi_select_indices")
-    if constraint_bounds is not None:
+    if log:
+        log_expected_hypervolume_improvement(
+            mu_objectives, variance_objectives,
+            _front_of(y_vector, n_evaluations, reference_point, constraint_bounds), reference_point,
+            constraint_bounds=constraint_bounds, out=acq.t)
+    elif constraint_bounds is not None:
         constrained_expected_hypervolume_improvement(
             mu_objectives, variance_objectives,
             _front_of(y_vector, n_evaluations, reference_point, constraint_bounds), reference_point,

@@ -35,15 +35,17 @@ from .acquisition import (ALL_BATCH_STRATEGIES, MES_BATCH_STRATEGIES, ExclusionM
                           select_batch_bucb,
                           select_batch_kb, select_batch_ts,
                           select_indices, thompson_draws,
-                          update_expected_hypervolume_improvement, update_hypervolume_improvement_exact)
+                          update_expected_hypervolume_improvement, update_hypervolume_improvement_exact,
+                          update_log_expected_hypervolume_improvement)
 
-ACQUISITIONS = ("sum_ucb", "hvi", "ehvi", "mes")
+ACQUISITIONS = ("sum_ucb", "hvi", "ehvi", "mes", "logehvi")
 DEFAULT_MES_SAMPLES = 8
 
 
 def _check_acquisition(acquisition):
     if acquisition not in ACQUISITIONS:
-        raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi', 'ehvi' or 'mes')")
+        raise ValueError(f"unknown acquisition {acquisition!r} (expected 'sum_ucb', 'hvi', 'ehvi', 'mes' "
+                         "or 'logehvi')")
 from .config import (DEFAULT_BATCH_SIZE, DEFAULT_BETA, DEFAULT_INITIAL_SAMPLES,
                      DEFAULT_LENGTH_SCALE, DEFAULT_PRIOR_MEAN, DEFAULT_PRIOR_VARIANCE,
                      check_fit_method, resolve_float_type)
@@ -238,7 +240,10 @@ class DeviceBackend:
         expected hypervolume improvement of the posterior (mu_objectives, variance_objectives) over
         that front (acquisition.ehvi_select_indices; not in the reference); "mes" with the max-value
         entropy search acquisition over the maxima of `mes_samples` posterior draws
-        (acquisition.mes_select_indices; not in the reference; up to 8 objectives, "top" or "gibbon").
+        (acquisition.mes_select_indices; not in the reference; up to 8 objectives, "top" or "gibbon");
+        "logehvi" with the natural logarithm of the EHVI (ehvi_select_indices with log=True; not in the
+        reference; "top" only): finite and ordered where "ehvi" underflows to 0.0 -- prefer it when the
+        length scales are long or the variance sits at its floor.
         batch_strategy "top" is the reference's batch (the batch_size best values of one
         acquisition array); "bucb" (not in the reference) takes every pick after the first from the
         UCB recomputed with the variance conditioned on the earlier picks
@@ -339,7 +344,7 @@ class DeviceBackend:
                 if not collectives_on(self.group):
                     return _record_indices(rec, batch_size)
                 return np.asarray(exchange_topq_rec(rec, batch_size, self.group)[1], dtype=np.int64)
-        if acquisition in ("hvi", "ehvi") and batch_size <= _lib.MAX_TOPQ:
+        if acquisition in ("hvi", "ehvi", "logehvi") and batch_size <= _lib.MAX_TOPQ:
             # the exact HVI and its top-q with exclusion in one device pass over this shard (the
             # EHVI: its scan, then the masked top-q), then the fused path's exchange
             # the shard's exclusion mask persists across iterations: only the new batch's rows
@@ -356,7 +361,7 @@ class DeviceBackend:
                                           self.bufs.variance_objectives, y_evaluated, len(y_evaluated),
                                           reference_point, self.cands, evaluated, batch_size,
                                           offset=self.offset, return_record=True, mask=self._excl_mask,
-                                          constraint_bounds=constraint_bounds)
+                                          constraint_bounds=constraint_bounds, log=acquisition == "logehvi")
             from .distributed import collectives_on, exchange_topq_rec
             if not collectives_on(self.group):
                 return _record_indices(rec, batch_size)
@@ -370,6 +375,11 @@ class DeviceBackend:
                                                     self.bufs.variance_objectives, y_evaluated,
                                                     len(y_evaluated), reference_point,
                                                     constraint_bounds=constraint_bounds)
+        if acquisition == "logehvi":
+            update_log_expected_hypervolume_improvement(self.bufs.acquisition_values, self.bufs.mu_objectives,
+                                                        self.bufs.variance_objectives, y_evaluated,
+                                                        len(y_evaluated), reference_point,
+                                                        constraint_bounds=constraint_bounds)
         # batches above BO_MAX_TOPQ: rounds of the standalone device selection (over the gathered
         # array when sharded)
         from .distributed import collectives_on
@@ -427,6 +437,10 @@ def optimize(x_vector, y_vector, kernel_matrices, k_star, mu_objectives, varianc
     `fit_method` "lbfgs" fits the length scales by L-BFGS-B over log ls with the device's analytic
     MLL gradient (kernels.optimize_hyperparams_mll, method="lbfgs": prior_variance stays as given);
     "powell", the default, is the reference's fit.  It is the backend's when `backend` is given.
+    `acquisition` "logehvi" (not in the reference; what "ehvi" takes, batch_strategy "top" only, outcome
+    constraints included) is the EHVI in log space (acquisition.log_expected_hypervolume_improvement):
+    prefer it to "ehvi" when the length scales are long or the variance sits at its floor, where "ehvi"
+    is exactly 0.0 at most candidates and a batch is completed in index order.
     `acquisition` "mes" (not in the reference; 1 to 8 objectives, batch_strategy "top" with any
     number of ranks, or "gibbon" on one rank) is the max-value entropy search acquisition
     (acquisition.max_value_entropy) over the maxima of `mes_samples` posterior draws
@@ -574,6 +588,12 @@ def _check_batch_strategy(batch_strategy, acquisition, batch_size, group=None):
         raise ValueError(f"acquisition='mes' supports batch_strategy='top' only (got {batch_strategy!r}): {why}; "
                          "a batch for the max-value entropy would need the variance conditioned on the earlier picks "
                          "(batch_strategy='gibbon' is that batch)")
+    if acquisition == "logehvi" and batch_strategy != "top":
+        why = {"bucb": "'bucb' conditions the UCB acquisition ('sum_ucb')",
+               "ts": "'ts' scores posterior draws, and the EHVI integrates over the posterior: it has no sampled form",
+               "kb": "'kb' (Kriging believer) integrates the linear EHVI while it selects; a believer over the log "
+                     "value is not built (use acquisition='ehvi' with 'kb')"}[batch_strategy]
+        raise ValueError(f"acquisition='logehvi' supports batch_strategy='top' only (got {batch_strategy!r}): {why}")
     if batch_strategy == "kb":
         if acquisition != "ehvi":
             raise ValueError("batch_strategy='kb' (Kriging believer) extends the front by believed observations: "
@@ -612,7 +632,7 @@ def _check_constraints(n_obj, n_con, constraint_bounds, acquisition, batch_strat
         raise ValueError(f"n_constraints must be >= 0 (got {n_con})")
     if n_con == 0 and constraint_bounds is None:
         return
-    if acquisition != "ehvi":
+    if acquisition not in ("ehvi", "logehvi"):
         why = {"sum_ucb": "'sum_ucb' takes negative values, so its product with a probability of feasibility "
                           "does not order the candidates",
                "hvi": "'hvi' scores UCB vectors, not a posterior that a probability of feasibility could weight"}
@@ -658,6 +678,9 @@ def _check_limits(n_obj, dim, total_samples, batch_size, acquisition="sum_ucb", 
     if acquisition == "ehvi" and n_obj > 4:
         raise ValueError(f"acquisition='ehvi' supports at most 4 objectives (got {n_obj}): the expected "
                          "hypervolume improvement's box decomposition is limited to n_obj <= 4")
+    if acquisition == "logehvi" and n_obj > 4:
+        raise ValueError(f"acquisition='logehvi' supports at most 4 objectives (got {n_obj}): the expected "
+                         "hypervolume improvement's box decomposition is limited to n_obj <= 4")
     if not 1 <= dim <= _lib.MAX_DIM:
         raise ValueError(f"the input dimension must be in [1, {_lib.MAX_DIM}] (got {dim})")
     if batch_size < 1:
@@ -681,6 +704,9 @@ class BayesianOptimization:
     grid), ``device``, ``acquisition`` ("sum_ucb", the reference's default; "hvi": exact
     hypervolume improvement of the UCB vectors over the evaluated Pareto front; or "ehvi": the
     expected hypervolume improvement of the posterior over that front, objectives independent; or
+    "logehvi": the natural logarithm of the EHVI, acquisition.log_expected_hypervolume_improvement, for what
+    "ehvi" takes with batch_strategy "top" -- prefer it where "ehvi" underflows to 0.0 (long length scales, the
+    variance at its floor); or
     "mes": max-value entropy search, acquisition.max_value_entropy, for 1 to 8 objectives and
     batch_strategy "top" or "gibbon", over the maxima of ``mes_samples`` posterior draws, default 8, drawn anew
     every iteration from the ``ts_seed`` generator with ``ts_features`` features),

@@ -22,7 +22,7 @@ SOURCES = ["bo_predict_d2.hip", "bo_predict_d4.hip", "bo_predict_d6.hip", "bo_pr
            "bo_predict_s2.hip", "bo_predict_s4.hip", "bo_predict_s6.hip", "bo_predict_s8.hip",
            "bo_predict.hip", "bo_gridconv.hip", "bo_fit.hip", "bo_lu.hip", "bo_select.hip", "bo_misc.hip", "bo_hvi.hip",
            "bo_powell.hip", "bo_bucb.hip", "bo_ehvi.hip", "bo_ts.hip", "bo_kb.hip",
-           "bo_mll_grad.hip", "bo_mes.hip", "bo_gibbon.hip"]
+           "bo_mll_grad.hip", "bo_mes.hip", "bo_gibbon.hip", "bo_logehvi.hip"]
 HEADERS = ["bo_common.h", "bo_cand.h", "bo_predict_impl.h", "bo_bucb_impl.h", "bo_ehvi_impl.h",
            os.path.join("..", "..", "include", "bo_amd.h")]
 ARCH = os.environ.get("BO_OFFLOAD_ARCH", "gfx950")

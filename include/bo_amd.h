@@ -499,6 +499,89 @@ int bo_constrained_ehvi(double* acq, double* pof_out, const double* mu, const do
                         const double* edges, const int32_t* n_edges, const int32_t* box_idx,
                         int32_t form, void* stream);
 
+/* The EHVI in log space (opt-in acquisition "logehvi"; LogEI / qLogEHVI: Ament et al., NeurIPS 2023).
+ * NOT in the reference: parity is unpinned by it (tests/logehvi_ref.py is the independent statement,
+ * in mpmath).  bo_expected_hypervolume_improvement returns one f64: psi is cut off at |z| = 40 and
+ * products of small factors underflow before that, so every candidate some tens of posterior standard
+ * deviations under the front gets exactly 0.0 and a batch that reaches into those zeros is filled in
+ * index order.  This scan returns the natural logarithm of the same quantity, finite and correctly
+ * ordered wherever the exact value is positive and its logarithm is an f64.  It is monotone in the
+ * EHVI: where the linear values are distinct and did not underflow it selects the same batch.  With
+ * the notation of bo_expected_hypervolume_improvement and bo_constrained_ehvi (sigma_k = sqrt(|var_k|),
+ * bo_hvi_boxes' boxes, the constraint rows after the objective rows):
+ *   psi_k(a) = sigma_k h(z),  z = (mu_k - a) / sigma_k,  h(z) = phi(z) + z Phi(z),  psi_k(+inf) = 0
+ *   F_bk     = psi_k(l_bk) - psi_k(u_bk)
+ *   T_b      = sum_k ln F_bk
+ *   L        = ln sum_b exp(T_b)  [ + sum_j ln P_j ,  P_j = Phi(zb_j) - Phi(za_j) ]
+ * LIMITS: sigma = 0 gives the limit psi(a) = max(mu - a, 0); a box with a zero factor contributes
+ * nothing; when the exact EHVI is 0 (no box has all factors positive, or n_boxes = 0) L = -inf;
+ * P_j = 0 (sigma = 0 outside the bounds, or lo = hi) gives -inf; the bounds (-inf, +inf) contribute
+ * exactly 0; NaN in any mu or var of any row, objective or constraint, gives NaN (selected first, as
+ * everywhere else).  z^2 >= 1e300 counts as psi = 0; likewise a constraint whose nearer tail
+ * argument t has t^2 past f64's range (t above about 1.3e154) gives ln P_j = -inf.
+ * -inf AND THE SELECTION: bo_select_topq / bo_select_topq_masked order NaN first, then descending
+ * value, ties by ascending index, and -inf is an ordinary value in that order, the lowest: a free
+ * candidate whose value is -inf IS selected once no higher value is left, with top_val = -inf and
+ * its own top_idx >= 0.  The "no candidate" record is told apart by top_idx = -1 alone (its
+ * top_val is -inf too).  So a batch larger than the number of candidates with a positive EHVI is
+ * completed by the -inf candidates in index order, exactly as the linear scan's zeros are.
+ * ARITHMETIC (bo_logehvi.hip states it in full): every psi is carried as an extended-range number
+ * m 2^e (an f64 mantissa, an integer exponent held in an f64), produced once per bound from the
+ * direct form for z >= 0, from exp(-z^2/2) [1/sqrt(2 pi) - |z| erfcx(|z| / sqrt 2) / 2] for
+ * -32 < z < 0 and from the series in 1 / z^2 (9 terms) below; the box differences, products and the
+ * running sum work on mantissas aligned by ldexp to a running maximum exponent, in box order, with
+ * no atomics; the logarithm is taken once per candidate.  ln P_j is ln(Q(t1) - Q(t2)) of the two
+ * tail terms while the nearer tail argument is below 6, and from there on comes from ln Q(z) =
+ * ln(erfcx(z / sqrt 2) / 2) - z^2 / 2 and a log-difference of the two tails.  A candidate's bits do
+ * not depend on its shard, on n or on ld.
+ * ROUNDING RULE: with L_ref the same quantity from the same f64 mu, var, boxes and bounds at 60
+ * digits and u = 2^-53, at every candidate
+ *   c(z)     = 1 + min(z, 0)^2                    (the conditioning of ln h in z; 1 + z^2 for ln Q)
+ *   kappa_bk = [psi(l) c(z_l) + psi(u) c(z_u)] / F_bk
+ *   w_b      = exp(T_b - ln sum_b exp T_b)        (the reference's weights, they sum to 1)
+ *   K        = sum_b w_b sum_k (kappa_bk + |ln F_bk|)  +  sum_j (kappa_j + |ln P_j|)
+ *   |L - L_ref| <= u [ C K + n_boxes + 2 ],   C = 8,
+ * kappa_j the same expression over the two tail terms of P_j; logpof_out alone meets
+ * |lp - lp_ref| <= u [ C sum_j (kappa_j + |ln P_j|) + 2 ].  Where L_ref is -inf or NaN the value is
+ * that.  C: the f64 restatement of this arithmetic (tests/logehvi_ref.py, logehvi_f64) measured a
+ * worst (|L - L_ref| / u - n_boxes - 2)+ / K of 2.81 on the CPU over z from +8 to -1e6 and on both
+ * sides of every branch switch, sigma from 1e-5 to 1e3, thin and wide boxes, 1 to 4 objectives and
+ * 0, 1 and 7 constraints (2.67 at z = -32.1 with one objective, the first point of the series;
+ * logpof alone 1.04); C is the smallest power of two at least twice that.
+ * ON THE DEVICE (MI355X, tests/test_gpu_logehvi.py, every candidate, both forms): the worst
+ * |L - L_ref| / bound is 0.357 (one objective, a one-point front), the worst fraction of logpof_out's
+ * own bound 0.176 (3 objectives, 5 constraints), 0.242 over the 1023 candidates of the motivating
+ * case; DESIGN.md section 19 lists the cases.
+ *
+ * bo_log_ehvi: the arguments of bo_constrained_ehvi, with the same checks, all before the device is
+ * touched (BO_ERR_ARG for lo > hi, a NaN bound, lo = +inf, hi = -inf, n_obj outside 1..4,
+ * n_con < 0, n_obj + n_con > BO_MAX_OBJ, con_lo / con_hi NULL with n_con > 0, a NULL acq / mu /
+ * var, n < 0, ld < n, n_boxes < 0, form outside 0..2, or the pointers of the form asked for
+ * missing); n = 0 returns BO_OK.  n_con = 0 is the plain form.  logpof_out (optional, device [n])
+ * receives sum_j ln P_j (0 without constraints; NaN where a constraint row holds NaN).
+ * Asynchronous on `stream`, capturable in a HIP graph, deterministic.  `form` as for the EHVI, and
+ * the direct and the table form give the same bits, but the table holds 16 bytes per edge and
+ * thread (mantissa and exponent).  ADMISSION RULE: the workgroup is the largest T in {256, 128, 64}
+ * with 16 S T <= 163840 bytes, i.e. T = 256 for S <= 40, 128 for S <= 80, 64 for S <= 160 --
+ * bo_logehvi_table_threads returns T, or 0 when no table fits, and then form 2 returns
+ * BO_ERR_UNSUPPORTED.  AUTO'S RULE, from profiles/logehvi_c3.jsonl (2^20 candidates, 2 objectives)
+ * and profiles/logehvi_c4.jsonl (2^21 candidates, 3 objectives), table against direct in one
+ * process: with 2 objectives the table form for S <= 20 only, where two 256-thread tables fit a CU
+ * (direct / table time 1.24x and 1.25x at S = 18 and 20; 0.84x, 0.87x and 0.87x at S = 22, 34 and
+ * 40, where one table leaves a CU with one wave per SIMD; 0.48x at S = 42 and 66 with 128
+ * threads); with 3 or 4 objectives the table form where its workgroup has at least 128 threads,
+ * S <= 80 (2.25x at S = 27, 1.58x at S = 51; 0.99x at S = 99 with 64 threads, so the direct form
+ * there; 4 objectives follow 3's rule and were not measured); with 1 objective (one box, one psi)
+ * the direct form.  COST against the "ehvi" scan in the same process, each in its faster form:
+ * 2.1x to 2.8x its time at 2 objectives (0.174 against 0.076 ms at a front of 8, 0.401 against
+ * 0.148 ms at 16), 3.4x to 4.1x at 3 objectives (0.955 against 0.281 ms at a front of 8); direct
+ * against direct it is 2.0x to 2.2x throughout; one constraint adds 4 to 13 %. */
+int bo_logehvi_table_threads(int64_t sum_edges);
+int bo_log_ehvi(double* acq, double* logpof_out, const double* mu, const double* var, int64_t ld,
+                int64_t n, int32_t n_obj, int32_t n_con, const double* con_lo, const double* con_hi,
+                const double* boxes, int64_t n_boxes, const double* edges, const int32_t* n_edges,
+                const int32_t* box_idx, int32_t form, void* stream);
+
 /* ------------------------------------------------------------------------------------
  * Max-value entropy search for multi-objective problems (MESMO: Belakaria, Deshwal & Doppa 2019,
  * after Wang & Jegelka 2017; opt-in acquisition "mes").  NOT in the reference: parity is unpinned
