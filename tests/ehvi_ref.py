@@ -3,6 +3,7 @@ statement and independently of the device's rearrangement of psi (bo_ehvi.hip), 
 mirror of the table form's admission rule (include/bo_amd.h).  PARITY UNPINNED by the reference,
 which has no EHVI; tests/test_ehvi.py pins this file against a Monte-Carlo mean of the box sum
 that tests/test_hvi.py pins against the brute-force hypervolume.
+The exact reference (mpmath, and the rounding rule the device is held to) is tests/ehvi_exact_ref.py.
 
     EHVI = sum_b prod_k [psi_k(l_bk) - psi_k(u_bk)],   psi_k(a) = E[(Y_k - a)+],  Y_k ~ N(mu_k, sigma_k^2)
 """
