@@ -7,7 +7,8 @@ propagates |d sqrt(v)| <= min(sqrt(dv), dv / sqrt(v_ref)), so candidate i's acqu
     tol_i = sum_o EPS_MU + beta_o min(sqrt(EPS_VAR), EPS_VAR / sqrt(std_var_ref[o, i]))
 -- ~1e-4 away from the data, ~1e-2 at a training point -- and the selection is judged tie-aware
 on the CPU acquisition array with that per-candidate bound (round 3 allowed 0.19 max|acq| and
-only asked each pick to lie within 2x that of the 16th best)."""
+only asked each pick to lie within 2x that of the 16th best).
+The counted f32 rounding bound of this kernel, at small shapes: tests/test_gpu_fp32_exact.py."""
 import numpy as np
 import pytest
 
